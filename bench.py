@@ -9,7 +9,11 @@ Default workload: 65,536 tables per GPU, uniform-random legal policy on device, 
 (obs version per --version), finished tables refilled with fresh seeds so the table count stays constant.
 Synthetic fixed-seed deals: game g uses seed (10000 + g/4, 0xd5dfaa4cef265cd7) (docs/src/perf/strength.md:19).
 
+A plain run measures the headline only; --full adds the extra workloads, the CPU baseline and the measured write ceiling of the
+encode roofline.  --dump-outputs DIR writes what the last timed cycle computed (rows, masks, actions, a seeded obs sample) as .npy.
+
   python bench.py --gpus 1 --steps 30 --warmup 10            # obs v4 (SP tables included; SP dominates the cycle)
+  python bench.py --gpus 1 --steps 30 --warmup 10 --full     # + workloads, cpu_baseline, measured write ceiling
   python bench.py --gpus 1 --steps 200 --warmup 30 --version 3  # obs v3 (no SP block): the env-step + encode path alone
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
@@ -212,11 +216,61 @@ def _phase_ticks(pool):
         return None
 
 
+DUMP_OBS_ROWS = 192  # --dump-outputs: decisions whose whole obs tensor is written (192 x 1012 x 34 f32 = 26 MB)
+DUMP_MAX_ROWS = 131072  # --dump-outputs: per-decision arrays (row, mask, action: 216 B a decision) of at most this many decisions
+DUMP_SEED = 20240601
+
+
+def _last_step_outputs(pools, views, a_prev, n):
+    """What the timed path handed its caller in the last timed cycle, over every pool of this rank (pool k's tables are k * n ..):
+    the row descriptors (table, seat, is_kan), the legal-action masks, the actions the policy chose and the encoded obs.  The
+    obs of a full pool is gigabytes, so a fixed, seeded sample of DUMP_OBS_ROWS decisions keeps its whole obs tensor."""
+    import numpy as np
+    import torch
+
+    rows, masks, acts, obs = [], [], [], []
+    for k, (pool, vw) in enumerate(zip(pools, views)):
+        nr = pool.n_rows[0]
+        r = pool.rows(0)
+        r[:, 0] += k * n
+        rows.append(r)
+        masks.append(vw["masks"][:nr].cpu().numpy())
+        acts.append(a_prev[k][:nr].cpu().numpy() if a_prev[k] is not None else np.zeros(0, np.int32))
+        obs.append((vw["obs_v"], nr))
+    rows, masks, acts = np.concatenate(rows), np.concatenate(masks), np.concatenate(acts)
+    total = len(rows)
+    rng = np.random.default_rng(DUMP_SEED)
+    sel = np.arange(total) if total <= DUMP_MAX_ROWS else np.sort(rng.choice(total, DUMP_MAX_ROWS, replace=False))
+    osel = np.sort(rng.choice(total, min(total, DUMP_OBS_ROWS), replace=False))
+    obs_sample, base = [], 0
+    for ob, nr in obs:  # gather the sampled decisions on the device, copy only those
+        local = osel[(osel >= base) & (osel < base + nr)] - base
+        if len(local):
+            obs_sample.append(ob[:nr][torch.as_tensor(local, dtype=torch.int64, device=ob.device)].cpu().numpy())
+        base += nr
+    C = obs[0][0].shape[1]
+    return {"rows": rows[sel].astype(np.float64), "row_index": sel.astype(np.float64),
+            "masks": masks[sel].astype(np.float32), "actions": acts[sel].astype(np.float64),
+            "obs": (np.concatenate(obs_sample) if obs_sample else np.zeros((0, C, 34), np.float32)).astype(np.float32),
+            "obs_row_index": osel.astype(np.float64)}
+
+
+def _write_outputs(out_dir, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array (float32 / float64)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def _measure(pool_cls, N, g0, world, dev, version, preroll, policy, steps, warmup, bufs, engine=None, barrier=None,
-             deal_algo=None, n_pools=1):
+             deal_algo=None, n_pools=1, dump=None):
     """One workload: N tables (as n_pools pools of N / n_pools tables, each on its own HIP stream), `preroll` untimed cycles (cheap
     v3 encode), `warmup` untimed and `steps` timed cycles of step + encode(+SP) + policy.  Returns the raw measurements (host wall
-    time, HIP-event kernel times, counters).
+    time, HIP-event kernel times, counters).  dump: a dict that receives the last timed cycle's outputs (_last_step_outputs).
 
     n_pools > 1 (--pools): the tables are INDEPENDENT, so the pool can be cut into halves that run the same cycle one after the
     other on two streams: while one half's SP kernel drains (its persistent workgroups hold every register of the chip until they
@@ -323,6 +377,8 @@ def _measure(pool_cls, N, g0, world, dev, version, preroll, policy, steps, warmu
         res["results"] = (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
     else:
         res["results"] = None
+    if dump is not None:
+        dump.update(_last_step_outputs(pools, views, a_prev, n))
     for pool in pools:
         pool.close()
     return res
@@ -392,8 +448,14 @@ def main():
     ap.add_argument("--pools", type=int, default=1,
                     help="cut the tables of a GPU into this many independent pools on their own HIP streams (same cycle, one pool after the "
                          "other): one pool's step / encode kernels run in the tail of the other's SP kernel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-matrix", action="store_true", help="skip the extra workloads (obs v3, no pre-roll, greedy policy)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the extra workloads (`workloads`), the CPU baseline (`cpu_baseline`) and the measured "
+                         "HBM write ceiling of the encode roofline; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed cycles, write what the last timed cycle handed its caller as DIR/<name>.npy (f32 / f64): "
+                         "rows (table, seat, is_kan), masks, actions, and the obs of a fixed, seeded sample of decisions")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-matrix", action="store_true", help="with --full: skip the extra workloads (obs v3, no pre-roll, greedy policy)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: spawn / join the --gpus N ranks, all-reduce one token over --dist-backend, print the rank "
                          "count on rank 0 and exit before any GPU work (CPU test of the launcher: tests/test_bench_contract.py)")
@@ -490,9 +552,12 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    dump = {} if args.dump_outputs else None
     r = _measure(TablePool, N, g0, world, dev, args.version, args.preroll, args.policy, args.steps, args.warmup, bufs, engine, barrier,
-                 n_pools=args.pools)
+                 n_pools=args.pools, dump=dump)
     steps, games, dt, rows_timed = r["steps"], r["games"], r["dt"], r["rows"]
+    if dump is not None:
+        _write_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"), dump)
     enc_ms, enc_launches, sp_ms, sp_launches, C = r["enc_ms"], r["enc_launches"], r["sp_ms"], r["sp_launches"], r["C"]
 
     if world > 1:
@@ -512,9 +577,9 @@ def main():
         rows_all = rows_timed
         collective_ranks = 1
 
-    # the other driver-timed workloads (N = 1 only, a few seconds each): where the headline sits between them
+    # the other driver-timed workloads (--full, N = 1 only, a few seconds each): where the headline sits between them
     matrix = None
-    if world == 1 and not args.no_matrix and args.policy == "random" and args.version == 4:
+    if args.full and world == 1 and not args.no_matrix and args.policy == "random" and args.version == 4:
         k = max(5, args.steps // 3)
         matrix = {
             "obs_v3_random": _brief(_measure(TablePool, N, g0, world, dev, 3, args.preroll, "random", 10 * k, 10, bufs)),
@@ -548,7 +613,7 @@ def main():
         enc_rows = 890 if args.version == 4 else C
         bytes_per_row = enc_rows * 34 * 4 + 46 + STATE_READ_BYTES
         achieved = rows_timed * bytes_per_row / (enc_ms * 1e-3) / 1e9 if enc_ms > 0 else 0.0
-        ceiling = _write_ceiling_gbs(bufs[0], int(rows_timed / max(args.steps, 1)) * enc_rows * 34 * 4)
+        ceiling = _write_ceiling_gbs(bufs[0], int(rows_timed / max(args.steps, 1)) * enc_rows * 34 * 4) if args.full else None
         # HBM traffic of the encode kernel from the separate rocprofv3 --pmc passes (tools/profile_round.sh ->
         # profiles/pmc_encode.json: WRITE_SIZE + 2 x FETCH_SIZE per decision), scaled to this run's rows per launch
         traffic = traffic_src = None
@@ -606,8 +671,8 @@ def main():
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS,
-                "frac_of_measured_write_ceiling": achieved / ceiling,
-                "measured_write_ceiling": ceiling,  # torch zero_ of one launch's obs bytes on this GPU, measured in this run
+                "frac_of_measured_write_ceiling": achieved / ceiling if ceiling else None,
+                "measured_write_ceiling": ceiling,  # --full: torch zero_ of one launch's obs bytes on this GPU, measured in this run
                 "traffic": traffic,
                 "traffic_unit": "B/launch",
                 "traffic_source": traffic_src,
@@ -629,7 +694,7 @@ def main():
             line["sp_schedule"] = r["sp_schedule"]
         if matrix:
             line["workloads"] = matrix
-        if not args.no_cpu_baseline and world == 1 and args.policy == "random":  # reported at N=1 only (rank 0)
+        if args.full and not args.no_cpu_baseline and world == 1 and args.policy == "random":  # --full, reported at N=1 only (rank 0)
             cb = cpu_baseline(args.version, args.cpu_budget, args.cpu_tables, args.cpu_preroll)
             # the published figure's unit, for the eye only: hanchan/h at the measured games-per-step ratio of the GPU run
             cb["hanchan_per_hour_equiv"] = cb["value"] * (games / max(steps, 1)) * 3600.0

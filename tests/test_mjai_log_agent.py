@@ -1,5 +1,5 @@
 """`engine_type == 'mjai-log'` (agent/py_agent.rs:24-37 -> agent/mjai_log.rs:12-150).  The reference's own
-`ExampleMjaiLogEngine` (mortal/engine.py:96-140, restated below; the reference file is only READ for a textual comparison) plays the challenger of
+`ExampleMjaiLogEngine` (mortal/engine.py:96-140, restated below and checked against its recorded behaviour) plays the challenger of
 OneVsThree and one side of TwoVsTwo against a 'mortal'-type engine; its reactions are explicit mjai events applied by the
 step kernel (mj_step_ev).  Checked against the oracle arena driven by the same two policies, and the engine's callbacks
 (set_player_ids / start_game / end_kyoku / end_game, GameState fields) against the reference's planning.
@@ -13,15 +13,14 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")
-REF = "/root/reference/mortal"
 KEY = 0xD5DFAA4CEF265CD7
 if HOST not in sys.path:
     sys.path.insert(0, HOST)
 
 
 def _example_engine_cls():
-    """Always the in-file restatement (the same engine on every host, no external code executed); when the reference is
-    present, test_example_engine_restatement_matches_the_reference compares the two texts."""
+    """Always the in-file restatement (the same engine on every host, no external code executed);
+    test_example_engine_restatement_matches_the_reference compares it with the reference engine's recorded behaviour."""
 
     class ExampleMjaiLogEngine:  # mortal/engine.py:96-140
         def __init__(self, name):
@@ -168,16 +167,22 @@ def test_unknown_engine_type_is_rejected():
 
 
 def test_example_engine_restatement_matches_the_reference():
-    """The restated ExampleMjaiLogEngine follows mortal/engine.py:96-140 statement for statement (text comparison only: the
-    reference module is never imported or executed)."""
-    path = os.path.join(REF, "engine.py")
-    if not os.path.exists(path):
-        pytest.skip("reference not present on this host")
-    src = open(path).read()
-    body = src[src.index("class ExampleMjaiLogEngine"):]
-    for needle in ("self.engine_type = 'mjai-log'", "def set_player_ids(self, player_ids", "def react_batch(self, game_states)",
-                   "assert events[0]['type'] == 'start_kyoku'", "cans = state.last_cans", "if cans.can_discard:",
-                   "tile = state.last_self_tsumo()", "'type': 'dahai'", "'actor': player_id", "'tsumogiri': True",
-                   "res.append('{\"type\":\"none\"}')", "def start_game(self, game_idx", "def end_kyoku(self, game_idx",
-                   "def end_game(self, game_idx"):
-        assert needle in body, needle
+    """The restated ExampleMjaiLogEngine behaves like mortal/engine.py:96-140: the reference class's engine type, player ids,
+    reactions on synthetic game states (dahai of the drawn tile, tsumogiri, when a discard is due; else none), no-op callbacks
+    and the start_kyoku assertion, recorded in tests/golden/reference_engines.json (tests/golden/record_reference_engines.py)."""
+    import recorded_engine as R
+
+    want = R.fixture()["example_engine"]
+    eng = _example_engine_cls()("logger")
+    assert (eng.engine_type, eng.name, eng.player_ids) == (want["engine_type"], want["name"], want["player_ids_before"])
+    eng.set_player_ids([0, 2, 1, 3])
+    assert eng.player_ids == want["player_ids"]
+    got = eng.react_batch(R.example_engine_states())
+    assert got == want["reactions"]
+    assert any(r != '{"type":"none"}' for r in got) and '{"type":"none"}' in got
+    assert [eng.start_game(0), eng.end_kyoku(0), eng.end_game(0, [25000] * 4)] == want["callbacks"]
+    bad = R.example_engine_states()[:1]
+    bad[0].events_json = json.dumps([{"type": "tsumo"}])
+    assert want["not_start_kyoku_raises"] == "AssertionError"
+    with pytest.raises(AssertionError):
+        eng.react_batch(bad)

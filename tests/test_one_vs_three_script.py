@@ -1,59 +1,47 @@
-"""BASELINE configs[0] literally: the reference's `mortal/one_vs_three.py` is launched UNCHANGED as a subprocess —
-`import prelude` (which imports torch.utils.tensorboard: compat/tensorboard), `from config import config` (compat/toml),
-`from libriichi.arena import OneVsThree` (this repository's package) — with a generated config.toml and two torch.save'd tiny
-random-init checkpoints, 8 hanchan (games_per_iter = 8), and its printed line `challenger rankings: [...]` is compared with the
-reference-shaped oracle loop driven by the same two networks.  This is INTEGRATION.md §1's recipe, verbatim, except that the
-subprocess has no GPU: a test-side sitecustomize (tests/host/sitecustomize_emu) points the arena at the host emulator build of
-the same kernels.  Skipped where /root/reference does not exist (the GPU box).
+"""BASELINE configs[0] from a script: a driver subprocess set up by INTEGRATION.md §1's recipe — repo root and compat/ first on
+PYTHONPATH, `torch.utils.tensorboard` (compat/tensorboard), the config.toml through `toml` (compat/toml), `from libriichi.arena
+import OneVsThree` (this repository's package) with a log_dir, 8 hanchan (games_per_iter = 8) — and its printed rankings are
+compared with the reference-shaped oracle loop driven by the same two engines.  The subprocess has no GPU: a test-side
+sitecustomize (tests/host/sitecustomize_emu) points the arena at the host emulator build of the same kernels.
 
-Round 6: the same test against the REAL library on an MI355X — `tools/r06_cfg0_gpu.sh` ships a scratch copy of
-the reference's mortal/ directory with one builder `gpurun` call (git-ignored, deleted afterwards), sets MORTAL_REF_DIR to it and
-MORTAL_AMD_CFG0_REAL=1: config devices 'cuda:0', no emulator injection, libmortal_amd.so loaded by the unchanged script; the oracle
-loop's two engines run on the same GPU.  The log of that run is kept under profiles/."""
+The two engines are the reference's MortalEngine over tiny random-init checkpoints (seeds 1 and 2), recorded by
+tests/golden/record_reference_engines.py (tests/golden/reference_*, case `cfg0`) and replayed by tests/recorded_engine.RecordedEngine:
+a decision whose obs or mask differs from what the reference engine saw fails the test.  MORTAL_AMD_CFG0_REAL=1: the same
+against the REAL library (no emulator injection, libmortal_amd.so on cuda:0)."""
 import os
-import re
+import json
 import subprocess
 import sys
 
-import pytest
-
-REF = os.environ.get("MORTAL_REF_DIR", "/root/reference/mortal")
 REAL = os.environ.get("MORTAL_AMD_CFG0_REAL") == "1"  # the real libmortal_amd.so on cuda:0 instead of the host emulator
-DEVICE = "cuda:0" if REAL else "cpu"
 KEY = 0x55DFAA4CEF265CD7  # a TOML integer is a signed 64-bit value (config.toml: seed_key)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")
 
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "one_vs_three.py")), reason="/root/reference not present")
-
 VERSION = 4
 
 
-def _save_checkpoint(ref_model, path, seed):
-    """What mortal/one_vs_three.py:27-35 reads: config.control.version, config.resnet.{conv_channels,num_blocks}, mortal, current_dqn."""
-    import torch
+def _driver(cfg_path):
+    """The subprocess: the config through compat/toml, the recorded engines, one OneVsThree.py_vs_py with a log_dir."""
+    import torch.utils.tensorboard  # noqa: F401  (compat/tensorboard)
+    import toml
 
-    torch.manual_seed(seed)
-    brain = ref_model.Brain(version=VERSION, conv_channels=16, num_blocks=1)
-    dqn = ref_model.DQN(version=VERSION)
-    torch.save({"config": {"control": {"version": VERSION}, "resnet": {"conv_channels": 16, "num_blocks": 1}},
-                "mortal": brain.state_dict(), "current_dqn": dqn.state_dict()}, path)
+    import recorded_engine as R
+    from libriichi.arena import OneVsThree
+
+    with open(cfg_path, encoding="utf-8") as f:
+        cfg = toml.load(f)["1v3"]
+    chal, cham = (R.RecordedEngine(R.decisions("cfg0", who), VERSION, cfg[who]["name"]) for who in R.ENGINES)
+    env = OneVsThree(disable_progress_bar=True, log_dir=cfg["log_dir"])
+    rankings = env.py_vs_py(challenger=chal, champion=cham, seed_start=(10000, cfg["seed_key"]), seed_count=cfg["games_per_iter"] // 4)
+    print("rankings " + json.dumps([int(x) for x in rankings]))
 
 
 def test_one_vs_three_script_runs_unchanged(oracle, tmp_path):
-    for p in (ROOT, os.path.join(ROOT, "compat"), HOST, REF):
-        if p not in sys.path:
-            sys.path.append(p)
-    import engine as ref_engine  # mortal/engine.py
-    import model as ref_model  # mortal/model.py
-    import torch
-
+    import recorded_engine as R
     import test_reference_engine as T
     from mortal_amd.pool import default_deal_algo
 
-    cham_pt, chal_pt = str(tmp_path / "champion.pth"), str(tmp_path / "challenger.pth")
-    _save_checkpoint(ref_model, cham_pt, 2)
-    _save_checkpoint(ref_model, chal_pt, 1)
     cfg = tmp_path / "config.toml"
     cfg.write_text(f"""
 [1v3]
@@ -63,52 +51,35 @@ iters = 1
 log_dir = '{tmp_path / "logs"}'
 
 [1v3.champion]
-device = '{DEVICE}'
-enable_compile = false
-enable_amp = false
-enable_rule_based_agari_guard = false
 name = 'champion'
-state_file = '{cham_pt}'
 
 [1v3.challenger]
-device = '{DEVICE}'
-enable_compile = false
-enable_amp = false
-enable_rule_based_agari_guard = false
 name = 'challenger'
-state_file = '{chal_pt}'
 
 [1v3.akochan]
 enabled = false
 """)
     # INTEGRATION.md §1: repo root and compat/ before anything else on PYTHONPATH; + the test-only emulator injection
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "compat")] + ([] if REAL else [os.path.join(HOST, "sitecustomize_emu")])),
-               MORTAL_CFG=str(cfg), OMP_NUM_THREADS="4")
+               OMP_NUM_THREADS="4")
     if REAL:
         env.pop("MORTAL_AMD_TEST_EMU", None)
     else:
         env["MORTAL_AMD_TEST_EMU"] = "1"
-    run = subprocess.run([sys.executable, os.path.join(REF, "one_vs_three.py")], cwd=REF, env=env, stdin=subprocess.DEVNULL,
+    code = f"import sys; sys.path.insert(0, {os.path.join(ROOT, 'tests')!r}); import test_one_vs_three_script as S; S._driver({str(cfg)!r})"
+    run = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), env=env, stdin=subprocess.DEVNULL,
                          capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
-    m = re.search(r"challenger rankings: \[\s*(\d+)\s+(\d+)\s+(\d+)\s+(\d+)\s*\]", run.stdout)
+    m = [ln for ln in run.stdout.splitlines() if ln.startswith("rankings ")]
     assert m, run.stdout[-2000:]
-    got = [int(x) for x in m.groups()]
+    got = json.loads(m[-1][len("rankings "):])
     assert sum(got) == 8
 
-    # the same two checkpoints through the reference's MortalEngine on the oracle loop (arena/game.rs:286-304)
-    def load(path, name):
-        st = torch.load(path, weights_only=True, map_location="cpu")
-        brain = ref_model.Brain(version=VERSION, conv_channels=16, num_blocks=1).eval().to(DEVICE)
-        dqn = ref_model.DQN(version=VERSION).eval().to(DEVICE)
-        brain.load_state_dict(st["mortal"])
-        dqn.load_state_dict(st["current_dqn"])
-        return ref_engine.MortalEngine(brain, dqn, is_oracle=False, version=VERSION, device=torch.device(DEVICE), enable_amp=False,
-                                       enable_rule_based_agari_guard=False, name=name)
-
-    want = T._oracle_rankings(oracle, load(chal_pt, "challenger"), load(cham_pt, "champion"), (10000, KEY), 2, VERSION, default_deal_algo())
-    assert got == want, (got, want, run.stdout[-500:])
-    print(f"cfg0 ({'libmortal_amd.so on ' + DEVICE if REAL else 'host emulator'}): challenger rankings {got} == oracle loop {want}; script stdout tail: {run.stdout[-300:]!r}")
+    # the same two engines on the oracle loop (arena/game.rs:286-304), and the rankings the reference engines reached there
+    chal, cham = (R.RecordedEngine(R.decisions("cfg0", who), VERSION, who) for who in R.ENGINES)
+    want = T._oracle_rankings(oracle, chal, cham, (10000, KEY), 2, VERSION, default_deal_algo())
+    assert got == want == R.fixture()["one_vs_three"]["cfg0"]["rankings"], (got, want, run.stdout[-500:])
+    print(f"cfg0 ({'libmortal_amd.so' if REAL else 'host emulator'}): challenger rankings {got} == oracle loop {want}; script stdout tail: {run.stdout[-300:]!r}")
     # log_dir side effect (one_vs_three.rs:127-129,195-225): one gzip'd mjai log per hanchan
     logs = sorted(os.listdir(tmp_path / "logs"))
     assert len(logs) == 8 and all(f.endswith(".json.gz") for f in logs), logs

@@ -1,44 +1,24 @@
 """the device-side Boltzmann-epsilon / top-p sampling of `DeviceEngine.react_batch_device`
 (mortal_amd/policy.py) against the reference's `MortalEngine._react_batch` exploration branch and `sample_top_p`
 (mortal/engine.py:72-94): identical nucleus support, matching sampling frequencies, greedy flags, never an illegal action.
-The reference functions are imported from /root/reference when present (here), else restated inline (the GPU box)."""
-import os
-import sys
-
+The reference's sampling frequencies on this file's fixture are recorded in tests/golden/reference_top_p_freq.npy
+(tests/golden/record_reference_engines.py)."""
 import numpy as np
 import pytest
 import torch
 
 from mortal_amd.policy import boltzmann_actions, nucleus_sample
 
-REF = "/root/reference/mortal"
+TOP_PS = [0.0, 0.3, 0.8, 1.0]
+N_DRAWS = 40000
 
 
-def _ref_sample_top_p():
-    if os.path.exists(os.path.join(REF, "engine.py")):
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        for p in (root, os.path.join(root, "compat"), REF):
-            if p not in sys.path:
-                sys.path.append(p)
-        import engine as ref_engine
+def _ref_frequencies(top_p):
+    """sample_top_p's action frequencies per fixture row, N_DRAWS draws after torch.manual_seed(12)."""
+    import recorded_engine
 
-        return ref_engine.sample_top_p
-
-    def sample_top_p(logits, p):  # mortal/engine.py:83-94, restated for hosts without the reference tree
-        from torch.distributions import Categorical
-
-        if p >= 1:
-            return Categorical(logits=logits).sample()
-        if p <= 0:
-            return logits.argmax(-1)
-        probs = logits.softmax(-1)
-        probs_sort, probs_idx = probs.sort(-1, descending=True)
-        probs_sum = probs_sort.cumsum(-1)
-        mask = probs_sum - probs_sort > p
-        probs_sort[mask] = 0.0
-        return probs_idx.gather(-1, probs_sort.multinomial(1)).squeeze(-1)
-
-    return sample_top_p
+    assert recorded_engine.fixture()["top_p"] == {"values": TOP_PS, "draws": N_DRAWS}
+    return np.load(recorded_engine.TOP_P_FREQ)[TOP_PS.index(top_p)]
 
 
 def _fixture(rows=6, seed=3):
@@ -53,20 +33,19 @@ def _fixture(rows=6, seed=3):
     return q, masks
 
 
-@pytest.mark.parametrize("top_p", [0.0, 0.3, 0.8, 1.0])
+@pytest.mark.parametrize("top_p", TOP_PS)
 def test_nucleus_frequencies_match_reference(top_p):
-    ref = _ref_sample_top_p()
     q, masks = _fixture()
     logits = (q / 0.7).masked_fill(~masks, -torch.inf)
-    n = 40000
+    n = N_DRAWS
     big = logits.repeat_interleave(n, 0)
     torch.manual_seed(11)
     ours = nucleus_sample(big, top_p).view(-1, n)
-    torch.manual_seed(12)
-    theirs = ref(big.clone(), top_p).view(-1, n)
+    ref = _ref_frequencies(top_p)
+    assert ref.shape == (logits.shape[0], 46)
     for r in range(logits.shape[0]):
         fo = np.bincount(ours[r].numpy(), minlength=46) / n
-        ft = np.bincount(theirs[r].numpy(), minlength=46) / n
+        ft = ref[r]
         assert set(np.flatnonzero(fo)) <= set(np.flatnonzero(masks[r].numpy())), "illegal action sampled"
         # same nucleus: an action either side draws with visible frequency is drawn by the other one too
         assert set(np.flatnonzero(fo > 4e-3)) <= set(np.flatnonzero(ft > 1e-3)), (r, top_p)

@@ -1,48 +1,22 @@
-"""BASELINE configs[0] as written: the reference's own `mortal/engine.py` (MortalEngine) and `mortal/model.py` (Brain, DQN),
-imported UNCHANGED from /root/reference with this repository's `libriichi` package on the path, playing
-`libriichi.arena.OneVsThree.py_vs_py` — the call `mortal/one_vs_three.py:77-97` makes — and checked against the
-reference-shaped oracle loop driven by the same two networks through the reference's list-of-ndarray contract.
+"""BASELINE configs[0]: the reference's own `mortal/engine.py` (MortalEngine) over `mortal/model.py` (Brain, DQN), random-init
+tiny models, playing `libriichi.arena.OneVsThree.py_vs_py` — the call `mortal/one_vs_three.py:77-97` makes — and checked against
+the reference-shaped oracle loop driven by the same two engines through the reference's list-of-ndarray contract.  The engines
+are recorded (tests/golden/record_reference_engines.py -> tests/golden/reference_*) and replayed by
+tests/recorded_engine.RecordedEngine: a decision whose obs or mask differs bit for bit from what the reference engine saw fails.
 
-Runs on CPU: the arena's device kernels execute on the host SIMT emulator (tests/host/emu), the networks on torch CPU.
-Skipped where /root/reference does not exist (the GPU box)."""
+Runs on CPU: the arena's device kernels execute on the host SIMT emulator (tests/host/emu)."""
 import os
 import sys
 
 import numpy as np
 import pytest
 
-REF = os.environ.get("MORTAL_REF_DIR", "/root/reference/mortal")
 REAL = os.environ.get("MORTAL_AMD_CFG0_REAL") == "1"  # tools/r06_cfg0_gpu.sh: the real libmortal_amd.so and the networks on cuda:0
-DEVICE = "cuda:0" if REAL else "cpu"
 KEY = 0xD5DFAA4CEF265CD7
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")
-
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "engine.py")), reason="/root/reference not present")
-
-
-@pytest.fixture(scope="module")
-def ref_modules():
-    for p in (ROOT, os.path.join(ROOT, "compat"), HOST, REF):
-        if p not in sys.path:
-            sys.path.append(p)  # the repository's `libriichi` must win over anything in the reference tree
-    import engine as ref_engine  # noqa: E402  (mortal/engine.py)
-    import model as ref_model  # noqa: E402  (mortal/model.py: imports libriichi.consts)
-
-    import libriichi
-
-    assert os.path.dirname(libriichi.__file__).startswith(ROOT)
-    return ref_engine, ref_model
-
-
-def _engine(ref_engine, ref_model, version, seed, name, **kw):
-    import torch
-
-    torch.manual_seed(seed)
-    brain = ref_model.Brain(version=version, conv_channels=16, num_blocks=1).to(DEVICE)  # "random-init tiny model"
-    dqn = ref_model.DQN(version=version).to(DEVICE)
-    return ref_engine.MortalEngine(brain, dqn, is_oracle=False, version=version, device=torch.device(DEVICE), name=name,
-                                   enable_amp=False, enable_quick_eval=True, enable_rule_based_agari_guard=False, **kw)
+if HOST not in sys.path:
+    sys.path.insert(0, HOST)
 
 
 def _oracle_rankings(oracle, chal, cham, seed_start, seed_count, version, deal_algo):
@@ -72,14 +46,14 @@ def _oracle_rankings(oracle, chal, cham, seed_start, seed_count, version, deal_a
 
 
 @pytest.mark.parametrize("version", [4, 2])
-def test_reference_engine_plays_one_vs_three(oracle, ref_modules, version):
+def test_reference_engine_plays_one_vs_three(oracle, version):
     from libriichi.arena import OneVsThree
 
     from mortal_amd import arena as A
 
-    ref_engine, ref_model = ref_modules
-    chal = _engine(ref_engine, ref_model, version, 1, "challenger")
-    cham = _engine(ref_engine, ref_model, version, 2, "champion")
+    import recorded_engine as R
+
+    chal, cham = (R.RecordedEngine(R.decisions(f"v{version}", who), version, who) for who in R.ENGINES)
     old = A.BatchRunner.pool_cls
     if not REAL:  # (REAL: the product's own TablePool over libmortal_amd.so)
         import emu_pool
@@ -93,5 +67,5 @@ def test_reference_engine_plays_one_vs_three(oracle, ref_modules, version):
     from mortal_amd.pool import default_deal_algo
 
     want = _oracle_rankings(oracle, chal, cham, (10000, KEY), 1, version, default_deal_algo())
-    assert sum(got) == 4 and got == want
-    print(f"reference engine.py + model.py, py_vs_py v{version} on {'libmortal_amd.so, ' + DEVICE if REAL else 'the host emulator'}: rankings {got} == oracle loop")
+    assert sum(got) == 4 and got == want == R.fixture()["one_vs_three"][f"v{version}"]["rankings"]
+    print(f"reference engine.py + model.py (recorded), py_vs_py v{version} on {'libmortal_amd.so' if REAL else 'the host emulator'}: rankings {got} == oracle loop")

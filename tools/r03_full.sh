@@ -15,7 +15,7 @@ timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/v4_stat
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/v3_stats -- python /root/repo/bench.py --steps 60 --warmup 20 --no-cpu-baseline --no-matrix --version 3 > $OUT/v3_stats.log 2>&1
 cd /root/repo; python tools/summarize_profiles.py $OUT r03 65536 > $OUT/summarize.log 2>&1; tail -2 $OUT/summarize.log
 cp profiles/r03_* profiles/pmc_encode.json $OUT/profiles/ 2>/dev/null
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-400 $OUT/bench.json
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-400 $OUT/bench.json
 cp $OUT/bench.json $OUT/profiles/r03_bench_v4.json
 timeout 300 python bench.py --gpus 2 --dist-backend gloo --tables 8192 --steps 10 --warmup 3 --preroll 256 --no-cpu-baseline --no-matrix 2> $OUT/gloo.err | grep '^{' > $OUT/profiles/r03_bench_gloo_2ranks_1gpu.json; echo "gloo 2-rank rc=$?"; cut -c1-300 $OUT/profiles/r03_bench_gloo_2ranks_1gpu.json
 timeout 300 python -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
