@@ -145,6 +145,8 @@ int mj_sp_phase_ticks(MjPool* pool, uint64_t* out8, void* stream);
  * queues: the wide workgroups give up after 50 ms, the sweep launch still finishes every parked row, one line on stderr).
  * mode: -1 auto (launches of at most max_rows rows; the default, also settable through MJ_SP_WIDE / MJ_SP_WIDE_MAX_ROWS /
  * MJ_SP_WIDE_GRID / MJ_SP_PROMO_MIN1 / _MIN2), 0 never, 1 every launch.  Arguments <= 0 keep the current value (mode: < -1).
+ * The environment is read when the pool is created and applied at its first obs-v4 mj_encode, unless this function was called first:
+ * then none of those variables applies to the pool.
  * Call it before the pool's first obs-v4 mj_encode (the spare work areas are sized then); afterwards only mode 0 / the thresholds change. */
 int mj_pool_set_sp_schedule(MjPool* pool, int mode, int max_rows, int wide_grid, int min_level1, int min_level2);
 /* out[0] launches that ran both kernels, [1] rows parked and finished by mj_k_sp_wide, [2] rows the sweep launch had to take (the two

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -116,14 +117,114 @@ std::vector<float> build_rbf(int n_max, int cap, int intervals) {
     return out;
 }
 
-size_t enc_lds_bytes(int version) {
+// pad: PoolKnobs::enc_lds_pad
+size_t enc_lds_bytes(int version, size_t pad) {
     int C = enc_rows_written(version);
     int tile_rows = ((C + ENC_PASSES - 1) / ENC_PASSES + 1) & ~1;
-    // MJ_ENC_LDS_PAD (measurement only): extra dynamic LDS per workgroup = fewer resident workgroups per CU (round 6: the encoder is FASTER
-    // with four than with five or six -- concurrent write streams, not occupancy, limit it)
-    static const size_t pad = getenv("MJ_ENC_LDS_PAD") ? (size_t)atoi(getenv("MJ_ENC_LDS_PAD")) : 0;
     return (size_t)tile_rows * 34 * 4 + ((sizeof(TableOne) + 15) & ~(size_t)15) + sizeof(EncDerived) + pad;
 }
+
+// The library's environment switches (diagnostics and tests; tools/README.md), read once per pool by mj_pool_create.  The SP
+// schedule's switches apply at the pool's first obs-v4 encode unless mj_pool_set_sp_schedule was called.
+struct PoolKnobs {
+    // MJ_SP_GRID caps mj_k_sp's workgroups (tests: few workgroups, many rows each); MJ_SP_WIDE (0 never / 1 every launch / unset: auto),
+    // MJ_SP_WIDE_MAX_ROWS, MJ_SP_WIDE_GRID, MJ_SP_PROMO_MIN1 / _MIN2 (the level sizes that park a row): mj_pool_set_sp_schedule's values
+    std::optional<int> sp_grid, sp_wide, sp_wide_max_rows, sp_wide_grid, sp_promo_min1, sp_promo_min2;
+    bool sp_wide_serial = false;    // MJ_SP_WIDE_SERIAL: the schedule's three launches one after the other (always in the emulator)
+    bool sp_wide_all_rows = false;  // MJ_SP_WIDE_ALL_ROWS (tests, serial only): the wide kernel alone first, it takes every row
+    bool sp_prof = false;           // MJ_SP_PROF: mj_k_sp's phase / pass timers, printed by mj_counters
+    // MJ_ENC_LDS_PAD (measurement only): extra dynamic LDS per encoder workgroup = fewer resident workgroups per CU (round 6: the
+    // encoder is FASTER with four than with five or six -- concurrent write streams, not occupancy, limit it)
+    size_t enc_lds_pad = 0;
+    int enc_grid = 256 * ENC_WPS;   // MJ_ENC_GRID: the persistent encoder's grid (ENC_PERSIST builds; default ENC_WPS per CU)
+#ifdef SP_ROWDUMP
+    std::string sp_rowdump;         // MJ_SP_ROWDUMP: file the per-row cost records of every SP launch are appended to
+#endif
+};
+
+PoolKnobs read_knobs() {
+    auto num = [](const char* name) { const char* v = getenv(name); return v ? std::optional<int>(atoi(v)) : std::nullopt; };
+    PoolKnobs K;
+    K.sp_grid = num("MJ_SP_GRID");
+    K.sp_wide = num("MJ_SP_WIDE");
+    K.sp_wide_max_rows = num("MJ_SP_WIDE_MAX_ROWS");
+    K.sp_wide_grid = num("MJ_SP_WIDE_GRID");
+    K.sp_promo_min1 = num("MJ_SP_PROMO_MIN1");
+    K.sp_promo_min2 = num("MJ_SP_PROMO_MIN2");
+#ifdef MJ_EMU
+    K.sp_wide_serial = true;  // (the emulator runs a launch to completion)
+#else
+    K.sp_wide_serial = getenv("MJ_SP_WIDE_SERIAL") != nullptr;
+#endif
+    K.sp_wide_all_rows = getenv("MJ_SP_WIDE_ALL_ROWS") != nullptr;
+    K.sp_prof = getenv("MJ_SP_PROF") != nullptr;
+    if (auto v = num("MJ_ENC_LDS_PAD")) K.enc_lds_pad = (size_t)*v;
+    if (auto v = num("MJ_ENC_GRID")) K.enc_grid = std::max(1, *v);
+#ifdef SP_ROWDUMP
+    if (const char* v = getenv("MJ_SP_ROWDUMP")) K.sp_rowdump = v;
+#endif
+    return K;
+}
+
+// HIP event pairs around timed launches, owned by a pool: pairs[0, n_pending) wait for collect(), the rest are free.  A launch
+// that fails between begin() and end() leaves its pair free.
+struct EventTimer {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;
+    size_t n_pending = 0;
+    int begin(hipStream_t s) {
+        if (n_pending == pairs.size()) {
+            hipEvent_t a = nullptr, b = nullptr;
+            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
+                if (a) hipEventDestroy(a);
+                return fail("hipEventCreate failed");
+            }
+            pairs.push_back({a, b});
+        }
+        HIP_OK(hipEventRecord(pairs[n_pending].first, s));
+        return 0;
+    }
+    int end(hipStream_t s) {
+        HIP_OK(hipEventRecord(pairs[n_pending++].second, s));
+        return 0;
+    }
+    void collect(double* total_ms, int64_t* launches) {  // the launches timed since the last call; their pairs become free
+        double tot = 0;
+        for (size_t i = 0; i < n_pending; i++) {
+            hipEventSynchronize(pairs[i].second);
+            float ms = 0;
+            hipEventElapsedTime(&ms, pairs[i].first, pairs[i].second);
+            tot += ms;
+        }
+        if (total_ms) *total_ms = tot;
+        if (launches) *launches = (int64_t)n_pending;
+        n_pending = 0;
+    }
+    ~EventTimer() {
+        for (auto& e : pairs) hipEventDestroy(e.first), hipEventDestroy(e.second);
+    }
+};
+
+struct SpResources {
+    SpWork* work = nullptr;     // grid areas (one per workgroup of mj_k_sp) + spare + wide_areas
+    int grid = 0;               // mj_k_sp's largest grid
+    int spare = 0;              // spare work areas = promotions per launch (small pools: mj_sp.hip "promotion"; 0 = this pool never promotes)
+    int wide_areas = 0;         // work areas of mj_k_sp_wide's own workgroups (= its largest grid)
+    int* queue = nullptr;       // [0] row queue head, [1..8] / [9..16] class counts / cursors of the row sort, [SP_Q_TAIL] head of the tail
+    uint32_t* order = nullptr;  // [max_rows] queue position -> row
+    uint8_t* cls = nullptr;     // [max_rows] cost class of a row
+    unsigned long long* err = nullptr;  // [SP_ERR_WORDS] counter words (mj_sp.hip SpErrWord)
+    hipStream_t stream2 = nullptr;      // mj_k_sp_promo's stream while mj_k_sp_wide runs on the caller's (spare > 0)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    unsigned long long* gaveup_host = nullptr;  // pinned: the device's count of wide workgroups that gave up waiting, copied behind every sweep
+    void release() {
+        hipFree(work); hipFree(queue); hipFree(order); hipFree(cls); hipFree(err);
+        if (stream2) hipStreamDestroy(stream2);
+        if (ev_fork) hipEventDestroy(ev_fork);
+        if (ev_join) hipEventDestroy(ev_join);
+        if (gaveup_host) hipHostFree(gaveup_host);
+        *this = SpResources();
+    }
+};
 
 std::vector<MjGatherEnt> build_gather() {
     std::vector<MjGatherEnt> v;
@@ -156,22 +257,13 @@ struct MjPool {
     int* n_rows_dev = nullptr;
     int* block_rows = nullptr;
     TableOne* snap = nullptr;
-    SpWork* sp_work = nullptr;      // lazily allocated on the first v4 encode: sp_grid areas (one per workgroup of mj_k_sp) + sp_spare spare ones
-    int sp_grid = 0;
-    int sp_wide_areas = 0;          // work areas of mj_k_sp_wide's own workgroups (= its largest grid)
-    int sp_spare = 0;               // spare work areas = promotions per launch (small pools: mj_sp.hip "promotion"; 0 = this pool never promotes)
+    PoolKnobs knobs;
+    SpResources sp;                 // allocated at the first obs-v4 encode (sp_setup)
     int sp_wide_mode = -1;          // -1 auto (launches of at most sp_wide_max_rows rows), 0 never, 1 always
-    int sp_wide_max_rows = 20000, sp_wide_grid = 0, sp_promo_min[4] = {0, 0, 0, 0};  // grid / thresholds 0 = by the launch's row count (mj_encode)
-    hipStream_t sp_stream2 = nullptr;   // mj_k_sp's stream while mj_k_sp_wide runs on the caller's
-    hipEvent_t sp_ev_fork = nullptr, sp_ev_join = nullptr;
+    int sp_wide_max_rows = 20000, sp_wide_grid = 0, sp_promo_min[4] = {0, 0, 0, 0};  // grid / thresholds 0 = by the launch's row count (sp_launch)
     uint64_t sp_hybrid_launches = 0;
-    unsigned long long* sp_gaveup_host = nullptr;  // pinned: the device's count of wide workgroups that gave up waiting, copied behind every sweep
-    bool sp_wide_off = false;       // the two kernels did not overlap on this system: the schedule switched itself off (see mj_encode)
+    bool sp_wide_off = false;       // the two kernels did not overlap on this system: the schedule switched itself off (see sp_launch)
     bool sp_sched_set = false;      // mj_pool_set_sp_schedule was called: the environment does not override it
-    int* sp_queue = nullptr;        // [0] row queue head, [1..8] / [9..16] class counts / cursors of the row sort, [SP_Q_TAIL] head of the tail
-    uint32_t* sp_order = nullptr;   // [max_rows] queue position -> row
-    uint8_t* sp_cls = nullptr;      // [max_rows] cost class of a row
-    unsigned long long* sp_err = nullptr;
     int* enc_flag = nullptr;        // [1] an encoder op list overflowed (reported with the SP overflows)
     int* n_rows_host = nullptr;  // pinned
     hipEvent_t ev_rows = nullptr;  // recorded right after the row counts' copy: mj_rows_count waits for it, not for the snapshot behind it
@@ -188,11 +280,9 @@ struct MjPool {
     uint64_t cycles = 0;
     int last_rows[2] = {0, 0};
     bool rows_valid = false;
-    // encode timing
+    // encode timing (mj_encode_timing; the SP launches are timed with it)
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events, sp_events;
-    double timed_ms = 0;
-    int64_t timed_launches = 0;
+    EventTimer enc_timer, sp_timer;
 };
 
 extern "C" {
@@ -325,6 +415,7 @@ MjPool* mj_pool_create(int n_tables, int version, int deal_algo, int max_rows) {
         return nullptr;
     }
     MjPool* P = new MjPool;
+    P->knobs = read_knobs();
     P->n_tables = n_tables;
     P->n_blocks = (n_tables + MJ_LANES - 1) / MJ_LANES;
     P->version[0] = P->version[1] = version;
@@ -337,7 +428,8 @@ MjPool* mj_pool_create(int n_tables, int version, int deal_algo, int max_rows) {
               hipMalloc(&P->block_rows, (size_t)P->n_blocks * 2 * sizeof(int)) == hipSuccess &&
               hipMalloc(&P->snap, (size_t)P->n_blocks * MJ_LANES * sizeof(TableOne)) == hipSuccess &&
               hipHostMalloc(&P->n_rows_host, 2 * sizeof(int)) == hipSuccess &&
-              hipMalloc(&P->counters, 8 * sizeof(unsigned long long)) == hipSuccess;
+              hipMalloc(&P->counters, 8 * sizeof(unsigned long long)) == hipSuccess &&
+              hipMalloc(&P->enc_flag, sizeof(int)) == hipSuccess && hipMemset(P->enc_flag, 0, sizeof(int)) == hipSuccess;
     if (!ok) {
         fail("device allocation failed");
         mj_pool_destroy(P);
@@ -347,7 +439,7 @@ MjPool* mj_pool_create(int n_tables, int version, int deal_algo, int max_rows) {
     for (int v = 1; v <= 4; v++) {
         const void* fn = v == 1 ? (const void*)mj_k_encode<1> : v == 2 ? (const void*)mj_k_encode<2>
                        : v == 3 ? (const void*)mj_k_encode<3> : (const void*)mj_k_encode<4>;
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds_bytes(v));
+        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds_bytes(v, P->knobs.enc_lds_pad));
     }
     return P;
 }
@@ -360,32 +452,19 @@ void mj_pool_destroy(MjPool* P) {
     hipFree(P->n_rows_dev);
     hipFree(P->block_rows);
     hipFree(P->snap);
-    hipFree(P->sp_work);
-    if (P->sp_stream2) hipStreamDestroy(P->sp_stream2);
-    if (P->sp_ev_fork) hipEventDestroy(P->sp_ev_fork);
-    if (P->sp_ev_join) hipEventDestroy(P->sp_ev_join);
-    hipFree(P->sp_queue);
-    hipFree(P->sp_order);
-    hipFree(P->sp_cls);
-    hipFree(P->sp_err);
+    P->sp.release();
     hipFree(P->enc_flag);
     hipFree(P->log);
     hipFree(P->log_len);
     hipFree(P->rp_script); hipFree(P->rp_off); hipFree(P->rp_cursor); hipFree(P->rp_ev_index);
     hipFree(P->rp_kyoku); hipFree(P->rp_tracked); hipFree(P->rp_label); hipFree(P->rp_kan_label);
     if (P->n_rows_host) hipHostFree(P->n_rows_host);
-    if (P->sp_gaveup_host) hipHostFree(P->sp_gaveup_host);
     if (P->ev_rows) hipEventDestroy(P->ev_rows);
     if (P->ev_snap) hipEventDestroy(P->ev_snap);
     hipFree(P->counters);
     hipFree(P->final_scores);
     hipFree(P->final_done);
-    for (auto* v : {&P->events, &P->sp_events})
-        for (auto& e : *v) {
-            hipEventDestroy(e.first);
-            hipEventDestroy(e.second);
-        }
-    delete P;
+    delete P;  // (the timing events: ~EventTimer)
 }
 
 int mj_pool_reset(MjPool* P, const uint64_t* nonces, const uint64_t* keys, const uint32_t* game_ids,
@@ -675,6 +754,176 @@ int mj_rows_count(MjPool* P, int32_t out[2], void* stream) {
 }
 const uint32_t* mj_rows_dev(MjPool* P, int agent) { return P ? P->rows[agent & 1] : nullptr; }
 
+static SpParams sp_params(const MjPool* P, int agent, float* obs, int n) {
+    SpParams kp{};
+    kp.snap = P->snap;
+    kp.rows = P->rows[agent & 1];
+    kp.n_rows = n;
+    kp.tables = g_tables.dev;
+    kp.obs = obs;
+    kp.work = P->sp.work;
+    kp.queue = P->sp.queue;
+    kp.order = P->sp.order;
+    kp.err = P->sp.err;
+    return kp;
+}
+
+// The SP kernels' resources, sized at the pool's first obs-v4 encode (mj_pool_set_sp_schedule may change the mode until then).
+// All or nothing: after a failure the pool is as it was, and the next v4 encode tries again.
+static int sp_setup(MjPool* P, int agent, float* obs, hipStream_t s) {
+    SpResources& R = P->sp;
+    const PoolKnobs& K = P->knobs;
+    struct Undo {  // releases whatever was allocated on every early return
+        SpResources* R;
+        ~Undo() { if (R) R->release(); }
+    } undo{&R};
+    HIP_OK(hipMalloc(&R.err, SP_ERR_WORDS * sizeof(unsigned long long)));
+    HIP_OK(hipMemset(R.err, 0, SP_ERR_WORDS * sizeof(unsigned long long)));
+    HIP_OK(hipMalloc(&R.order, (size_t)P->max_rows * sizeof(uint32_t)));
+    HIP_OK(hipMalloc(&R.cls, (size_t)P->max_rows));
+    // persistent workgroups: SP_WGS per CU, one decision row each at a time; never more than the rows of a launch (small pools: small work area)
+    R.grid = std::min(256 * SP_WGS, P->max_rows);
+    if (K.sp_grid) R.grid = std::max(1, std::min(R.grid, *K.sp_grid));
+    if (!P->sp_sched_set) {
+        if (K.sp_wide) P->sp_wide_mode = *K.sp_wide;
+        if (K.sp_wide_max_rows) P->sp_wide_max_rows = *K.sp_wide_max_rows;
+        if (K.sp_wide_grid) P->sp_wide_grid = std::max(1, *K.sp_wide_grid);
+        if (K.sp_promo_min1) P->sp_promo_min[1] = std::max(1, *K.sp_promo_min1);
+        if (K.sp_promo_min2) P->sp_promo_min[2] = std::max(1, *K.sp_promo_min2);
+    }
+    R.spare = P->sp_wide_mode == 0 ? 0 : std::min(SP_PROMO_CAP, std::max(8, P->n_tables / 4) & ~1);
+    if (P->sp_wide_mode < 0 && P->n_tables > P->sp_wide_max_rows) R.spare = 0;  // (a launch has about as many rows as the pool has tables)
+    R.wide_areas = R.spare ? std::min(256, std::max(2, P->n_tables / 16)) : 0;  // (a 64-table test pool does not need 2 GB of work areas)
+    const int areas = R.grid + R.spare + R.wide_areas;
+    HIP_OK(hipMalloc(&R.work, (size_t)areas * sizeof(SpWork)));
+    for (int g = 0; g < areas; g++) {
+        HIP_OK(hipMemsetAsync(R.work[g].tag, 0, sizeof(R.work[g].tag), s));  // empty hash sets ...
+        HIP_OK(hipMemsetAsync(&R.work[g].epoch, 0, sizeof(R.work[g].epoch) + sizeof(R.work[g].pad_), s));  // ... at epoch 0
+    }
+    HIP_OK(hipMalloc(&R.queue, SP_Q_WORDS * sizeof(int)));
+    if (R.spare) {
+        HIP_OK(hipStreamCreateWithFlags(&R.stream2, hipStreamNonBlocking));
+        HIP_OK(hipEventCreateWithFlags(&R.ev_fork, hipEventDisableTiming));
+        HIP_OK(hipEventCreateWithFlags(&R.ev_join, hipEventDisableTiming));
+        HIP_OK(hipHostMalloc(&R.gaveup_host, sizeof(unsigned long long)));
+        *R.gaveup_host = 0ull;
+        // One empty launch of the pair now: the HIP runtime sizes a queue's scratch at the first launch that needs it, and a caller
+        // whose allocator has taken the whole HBM by then (torch's caching allocator under a growing batch) turns that into
+        // HSA_STATUS_ERROR_OUT_OF_RESOURCES in the middle of a run -- at pool set-up it is an ordinary, early failure.
+        HIP_OK(hipMemsetAsync(R.queue, 0, SP_Q_WORDS * sizeof(int), s));
+        HIP_OK(hipStreamSynchronize(s));
+        SpParams w = sp_params(P, agent, obs, 0);
+        w.sweep = 1;
+        hipLaunchKernelGGL(mj_k_sp_wide, dim3(1), dim3(SP_WIDE_THREADS), 0, s, w);
+        hipLaunchKernelGGL(mj_k_sp_promo, dim3(1), dim3(SP_THREADS), 0, R.stream2, w);
+        HIP_OK(hipStreamSynchronize(R.stream2));
+        HIP_OK(hipStreamSynchronize(s));
+        HIP_OK(hipGetLastError());
+    }
+    undo.R = nullptr;
+    return 0;
+}
+
+#ifdef SP_ROWDUMP
+// (debug) MJ_SP_ROWDUMP: the per-row cost records of every launch appended to that file, one synchronous copy per launch
+static int rowdump_begin(MjPool* P, SpParams& kp, hipStream_t s) {
+    HIP_OK(hipMalloc(&kp.rowdump, (size_t)kp.n_rows * 48));
+    HIP_OK(hipMemsetAsync(kp.rowdump, 0, (size_t)kp.n_rows * 48, s));
+    HIP_OK(hipMemsetAsync(P->sp.err + SP_ERR_DUMP_T0, 0xFF, 8, s));
+    HIP_OK(hipMemsetAsync(P->sp.err + SP_ERR_DUMP_NARROW, 0, 24, s));
+    return 0;
+}
+static int rowdump_end(MjPool* P, const SpParams& kp, hipStream_t s) {
+    const int n = kp.n_rows;
+    std::vector<uint32_t> h((size_t)n * 12);
+    int q[SP_Q_WORDS];
+    HIP_OK(hipMemcpyAsync(h.data(), kp.rowdump, (size_t)n * 48, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(q, P->sp.queue, sizeof(q), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    hipFree(kp.rowdump);
+    if (FILE* f = fopen(P->knobs.sp_rowdump.c_str(), "ab")) {
+        uint32_t hdr[12] = {0xFFFFFFFFu, (uint32_t)n};
+        unsigned long long tt[4];
+        HIP_OK(hipMemcpy(tt, P->sp.err + SP_ERR_DUMP_T0, sizeof tt, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 4; k++) hdr[2 + k] = (uint32_t)tt[k];  // first workgroup in, last narrow / wide out of the row loop, end of the tail
+        fwrite(hdr, 4, 12, f);
+        uint32_t cc[12];
+        for (int k = 0; k < 12; k++) cc[k] = k < 8 ? (uint32_t)q[1 + k] : 0u;
+        fwrite(cc, 4, 12, f);
+        for (int i = 0; i < n; i++)
+            if (h[(size_t)i * 12 + 7]) fwrite(&h[(size_t)i * 12], 4, 12, f);
+        fclose(f);
+    }
+    return 0;
+}
+#endif
+
+// One SP launch over the n rows just encoded: the row order, then mj_k_sp alone or the small-pool schedule
+static int sp_launch(MjPool* P, int agent, float* obs, int n, hipStream_t s) {
+    SpResources& R = P->sp;
+    HIP_OK(hipMemsetAsync(R.queue, 0, SP_Q_WORDS * sizeof(int), s));
+    SpParams kp = sp_params(P, agent, obs, n);
+    kp.prof = P->knobs.sp_prof ? R.err : nullptr;
+#ifdef SP_ROWDUMP
+    if (!P->knobs.sp_rowdump.empty() && rowdump_begin(P, kp, s)) return -1;
+#endif
+    const int grid = std::min(n, R.grid);
+    // The schedule needs mj_k_sp_wide and mj_k_sp_promo side by side.  Where they do not overlap -- more streams in the process than the
+    // runtime has hardware queues, so that the promo kernel queues up BEHIND the spinning wide kernel -- the wide workgroups give up
+    // after SP_WIDE_TIMEOUT, the sweep launch still produces the same obs, and the give-ups (copied to pinned memory behind every
+    // sweep) switch the schedule off for this pool: one slow launch, then mj_k_sp alone as in round 5.
+    if (P->sp_wide_mode < 0 && R.gaveup_host && *R.gaveup_host && !P->sp_wide_off) {  // (auto mode only: mode 1 = every launch, as asked)
+        P->sp_wide_off = true;
+        fprintf(stderr, "[mortal_amd] small-pool SP schedule switched off for this pool: mj_k_sp_wide and mj_k_sp_promo did not run side by side "
+                        "(%llu wide workgroups gave up waiting; more concurrent streams than hardware queues?)\n", *R.gaveup_host);
+    }
+    const bool hybrid = R.spare > 0 && !P->sp_wide_off && (P->sp_wide_mode > 0 || (P->sp_wide_mode < 0 && n <= P->sp_wide_max_rows));
+    kp.promo_cap = hybrid ? R.spare : 0;
+    // Defaults measured on MI355X (tools/r06_sweep.sh): up to ~12 k rows 64 wide workgroups (a quarter of the CUs),
+    // rows parked at >= 1,200 level-1 states (or >= 400 level-2 states, before that level is expanded); up to ~20 k rows 32 wide
+    // workgroups and 1,600 level-1 states; beyond that a launch keeps all CUs for mj_k_sp (sp_wide_max_rows).  The root level is never
+    // parked (nothing is known yet), level 0 is not expanded.
+    kp.promo_min[0] = kp.promo_min[3] = 1 << 30;
+    kp.promo_min[1] = P->sp_promo_min[1] > 0 ? P->sp_promo_min[1] : n <= 12000 ? 1200 : 1600;
+    kp.promo_min[2] = P->sp_promo_min[2] > 0 ? P->sp_promo_min[2] : n <= 12000 ? 400 : 1 << 30;
+    kp.n_narrow = grid;
+    // queue order: rows counting-sorted by cost class, heaviest first (inside the timed mj_k_sp region)
+    hipLaunchKernelGGL(mj_k_order_classify, dim3((n + 255) / 256), dim3(256), 0, s, P->snap, kp.rows, n, R.cls, R.queue + 1);
+    hipLaunchKernelGGL(mj_k_order_scatter, dim3((n + 255) / 256), dim3(256), 0, s, R.cls, n, R.queue + 1, R.queue + 9, R.order);
+    if (!hybrid) {
+        hipLaunchKernelGGL(mj_k_sp, dim3(grid), dim3(SP_THREADS), 0, s, kp);
+    } else {
+        // mj_k_sp_wide FIRST and on the caller's stream (its few workgroups take a whole CU each and must be resident before the 1,024
+        // workgroups of mj_k_sp fill the chip), mj_k_sp on the second stream behind the row order, then the sweep behind both.
+        // The emulator runs a launch to completion: there (and with MJ_SP_WIDE_SERIAL=1) the sweep alone takes the parked rows.
+        P->sp_hybrid_launches++;
+        const int wgrid = std::min(R.wide_areas, P->sp_wide_grid > 0 ? P->sp_wide_grid : n <= 12000 ? 64 : 32);
+        if (P->knobs.sp_wide_serial) {
+            if (P->knobs.sp_wide_all_rows) {  // (tests) the wide kernel alone first: with no producer to wait for it takes EVERY row of the queue itself
+                SpParams spw = kp;
+                spw.n_narrow = 0;
+                spw.work = kp.work + grid;  // (its own areas: work + n_narrow + promo_cap + block, as in the concurrent launch)
+                hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, spw);
+            }
+            hipLaunchKernelGGL(mj_k_sp_promo, dim3(grid), dim3(SP_THREADS), 0, s, kp);
+        } else {
+            HIP_OK(hipEventRecord(R.ev_fork, s));
+            hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, kp);
+            HIP_OK(hipStreamWaitEvent(R.stream2, R.ev_fork, 0));
+            hipLaunchKernelGGL(mj_k_sp_promo, dim3(grid), dim3(SP_THREADS), 0, R.stream2, kp);
+            HIP_OK(hipEventRecord(R.ev_join, R.stream2));
+            HIP_OK(hipStreamWaitEvent(s, R.ev_join, 0));
+        }
+        kp.sweep = 1;
+        hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, kp);
+        HIP_OK(hipMemcpyAsync(R.gaveup_host, R.err + SP_ERR_WIDE_GAVEUP, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    }
+#ifdef SP_ROWDUMP
+    if (kp.rowdump && rowdump_end(P, kp, s)) return -1;
+#endif
+    return 0;
+}
+
 int mj_encode(MjPool* P, int agent, float* obs, uint8_t* masks, void* stream) {
     if (!P) return fail("null pool");
     if (!P->rows_valid) return fail("mj_rows_count must be called after mj_step and before mj_encode");
@@ -695,23 +944,13 @@ int mj_encode(MjPool* P, int agent, float* obs, uint8_t* masks, void* stream) {
     ep.rbf_6 = g_tables.rbf_6;
     ep.rbf_12 = g_tables.rbf_12;
     ep.rbf_23 = g_tables.rbf_23;
-    if (!P->enc_flag) {
-        HIP_OK(hipMalloc(&P->enc_flag, sizeof(int)));
-        HIP_OK(hipMemset(P->enc_flag, 0, sizeof(int)));
-    }
     ep.err_flag = P->enc_flag;
-    size_t lds = enc_lds_bytes(ep.version);
+    size_t lds = enc_lds_bytes(ep.version, P->knobs.enc_lds_pad);
     hipStream_t s = (hipStream_t)stream;
     if (wait_snapshot(P, s)) return -1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (P->timing) {
-        HIP_OK(hipEventCreate(&e0));
-        HIP_OK(hipEventCreate(&e1));
-        HIP_OK(hipEventRecord(e0, s));
-    }
+    if (P->timing && P->enc_timer.begin(s)) return -1;
 #if ENC_PERSIST
-    static const int enc_grid_max = getenv("MJ_ENC_GRID") ? std::max(1, atoi(getenv("MJ_ENC_GRID"))) : 256 * ENC_WPS;  // persistent: ENC_WPS workgroups per CU
-    const int egrid = std::min(n, enc_grid_max);
+    const int egrid = std::min(n, P->knobs.enc_grid);
 #else
     const int egrid = n;
 #endif
@@ -721,185 +960,16 @@ int mj_encode(MjPool* P, int agent, float* obs, uint8_t* masks, void* stream) {
         case 3: hipLaunchKernelGGL(mj_k_encode<3>, dim3(egrid), dim3(ENC_THREADS), lds, s, ep); break;
         default: hipLaunchKernelGGL(mj_k_encode<4>, dim3(egrid), dim3(ENC_THREADS), lds, s, ep); break;
     }
-    if (P->timing) {
-        HIP_OK(hipEventRecord(e1, s));
-        P->events.push_back({e0, e1});
-    }
+    if (P->timing && P->enc_timer.end(s)) return -1;
     HIP_OK(hipGetLastError());
-    if (ep.version == 4) {  // SP block, rows 889..1011
-        // one decision row per persistent workgroup (mj_sp.hip: mj_k_sp).  Round 4 also built a per-phase pipeline (every phase its own launch
-        // over the state graphs of ALL rows: 34.8 ms against 21.9 ms, DESIGN.md section 6, profiles/r04_spg_*); it left the tree in round 5
-        // (git: mortal_amd/csrc/mj_sp2.hip up to commit 73bd82e).
-        if (!P->sp_err) {
-            HIP_OK(hipMalloc(&P->sp_err, 32 * sizeof(unsigned long long)));
-            HIP_OK(hipMemset(P->sp_err, 0, 32 * sizeof(unsigned long long)));
-            HIP_OK(hipMalloc(&P->sp_order, (size_t)P->max_rows * sizeof(uint32_t)));
-            HIP_OK(hipMalloc(&P->sp_cls, (size_t)P->max_rows));
-        }
-        hipEvent_t s0 = nullptr, s1 = nullptr;
-        if (P->timing) {
-            HIP_OK(hipEventCreate(&s0));
-            HIP_OK(hipEventCreate(&s1));
-            HIP_OK(hipEventRecord(s0, s));
-        }
-        {
-            if (!P->sp_work) {
-                P->sp_grid = 256 * SP_WGS;  // persistent workgroups: SP_WGS per CU, one decision row each at a time
-                if (P->sp_grid > P->max_rows) P->sp_grid = P->max_rows;  // never more rows than that in a launch (small pools: small work area)
-                if (const char* g = getenv("MJ_SP_GRID")) P->sp_grid = std::max(1, std::min(P->sp_grid, atoi(g)));  // tests: few workgroups, many rows each (the row-to-row paths)
-                // promotion of large rows to mj_k_sp_wide (mj_sp.hip): MJ_SP_WIDE = 0 never / 1 every launch / unset: launches of at most
-                // MJ_SP_WIDE_MAX_ROWS rows; MJ_SP_WIDE_GRID wide workgroups; MJ_SP_PROMO_MIN1 / _MIN2: the level sizes that park a row
-                if (!P->sp_sched_set) {
-                    if (const char* g = getenv("MJ_SP_WIDE")) P->sp_wide_mode = atoi(g);
-                    if (const char* g = getenv("MJ_SP_WIDE_MAX_ROWS")) P->sp_wide_max_rows = atoi(g);
-                    if (const char* g = getenv("MJ_SP_WIDE_GRID")) P->sp_wide_grid = std::max(1, atoi(g));
-                    if (const char* g = getenv("MJ_SP_PROMO_MIN1")) P->sp_promo_min[1] = std::max(1, atoi(g));
-                    if (const char* g = getenv("MJ_SP_PROMO_MIN2")) P->sp_promo_min[2] = std::max(1, atoi(g));
-                }
-                P->sp_spare = P->sp_wide_mode == 0 ? 0 : std::min(SP_PROMO_CAP, std::max(8, P->n_tables / 4) & ~1);
-                P->sp_wide_areas = P->sp_spare ? std::min(256, std::max(2, P->n_tables / 16)) : 0;  // (a 64-table test pool does not need 2 GB of work areas)
-                if (P->sp_wide_mode < 0 && P->n_tables > P->sp_wide_max_rows) P->sp_spare = 0;  // (a launch has about as many rows as the pool has tables)
-                const int areas = P->sp_grid + P->sp_spare + P->sp_wide_areas;  // + one per workgroup of mj_k_sp_wide (its own rows)
-                HIP_OK(hipMalloc(&P->sp_work, (size_t)areas * sizeof(SpWork)));
-                for (int g = 0; g < areas; g++) {
-                    HIP_OK(hipMemsetAsync(P->sp_work[g].tag, 0, sizeof(P->sp_work[g].tag), s));  // empty hash sets ...
-                    HIP_OK(hipMemsetAsync(&P->sp_work[g].epoch, 0, sizeof(P->sp_work[g].epoch) + sizeof(P->sp_work[g].pad_), s));  // ... at epoch 0
-                }
-                HIP_OK(hipMalloc(&P->sp_queue, SP_Q_WORDS * sizeof(int)));
-                if (P->sp_spare) {
-                    HIP_OK(hipStreamCreateWithFlags(&P->sp_stream2, hipStreamNonBlocking));
-                    HIP_OK(hipEventCreateWithFlags(&P->sp_ev_fork, hipEventDisableTiming));
-                    HIP_OK(hipEventCreateWithFlags(&P->sp_ev_join, hipEventDisableTiming));
-                    // One empty launch of the pair now: the HIP runtime sizes a queue's scratch at the first launch that needs it, and a caller
-                    // whose allocator has taken the whole HBM by then (torch's caching allocator under a growing batch) turns that into
-                    // HSA_STATUS_ERROR_OUT_OF_RESOURCES in the middle of a run -- at pool set-up it is an ordinary, early failure.
-                    HIP_OK(hipMemsetAsync(P->sp_queue, 0, SP_Q_WORDS * sizeof(int), s));
-                    HIP_OK(hipStreamSynchronize(s));
-                    SpParams w{};
-                    w.snap = P->snap;
-                    w.rows = P->rows[agent & 1];
-                    w.n_rows = 0;
-                    w.tables = g_tables.dev;
-                    w.obs = obs;
-                    w.work = P->sp_work;
-                    w.queue = P->sp_queue;
-                    w.order = P->sp_order;
-                    w.err = P->sp_err;
-                    w.sweep = 1;
-                    hipLaunchKernelGGL(mj_k_sp_wide, dim3(1), dim3(SP_WIDE_THREADS), 0, s, w);
-                    hipLaunchKernelGGL(mj_k_sp_promo, dim3(1), dim3(SP_THREADS), 0, P->sp_stream2, w);
-                    HIP_OK(hipStreamSynchronize(P->sp_stream2));
-                    HIP_OK(hipStreamSynchronize(s));
-                    HIP_OK(hipGetLastError());
-                }
-            }
-            HIP_OK(hipMemsetAsync(P->sp_queue, 0, SP_Q_WORDS * sizeof(int), s));
-            SpParams sp;
-            sp.snap = P->snap;
-            sp.rows = P->rows[agent & 1];
-            sp.n_rows = n;
-            sp.tables = g_tables.dev;
-            sp.obs = obs;
-            sp.work = P->sp_work;
-            sp.queue = P->sp_queue;
-            sp.order = P->sp_order;
-            sp.err = P->sp_err;
-            sp.prof = getenv("MJ_SP_PROF") ? P->sp_err : nullptr;
-            sp.rowdump = nullptr;
-            static const char* rowdump_path = getenv("MJ_SP_ROWDUMP");  // (debug) per-row cost records appended to this file, one synchronous copy per launch
-            if (rowdump_path) {
-                HIP_OK(hipMalloc(&sp.rowdump, (size_t)n * 48));
-                HIP_OK(hipMemsetAsync(sp.rowdump, 0, (size_t)n * 48, s));
-                HIP_OK(hipMemsetAsync(P->sp_err + 28, 0xFF, 8, s));
-                HIP_OK(hipMemsetAsync(P->sp_err + 29, 0, 24, s));
-            }
-            int grid = n < P->sp_grid ? n : P->sp_grid;
-            // The schedule needs mj_k_sp_wide and mj_k_sp_promo side by side.  Where they do not overlap -- more streams in the process than the
-            // runtime has hardware queues, so that the promo kernel queues up BEHIND the spinning wide kernel -- the wide workgroups give up
-            // after SP_WIDE_TIMEOUT, the sweep launch still produces the same obs, and the give-ups (copied to pinned memory behind every
-            // sweep) switch the schedule off for this pool: one slow launch, then mj_k_sp alone as in round 5.
-            if (P->sp_wide_mode < 0 && P->sp_gaveup_host && *P->sp_gaveup_host && !P->sp_wide_off) {  // (auto mode only: mode 1 = every launch, as asked)
-                P->sp_wide_off = true;
-                fprintf(stderr, "[mortal_amd] small-pool SP schedule switched off for this pool: mj_k_sp_wide and mj_k_sp_promo did not run side by side "
-                                "(%llu wide workgroups gave up waiting; more concurrent streams than hardware queues?)\n", *P->sp_gaveup_host);
-            }
-            const bool hybrid = P->sp_spare > 0 && !P->sp_wide_off && (P->sp_wide_mode > 0 || (P->sp_wide_mode < 0 && n <= P->sp_wide_max_rows));
-            sp.promo_cap = hybrid ? P->sp_spare : 0;
-            // Defaults measured on MI355X (tools/r06_sweep.sh): up to ~12 k rows 64 wide workgroups (a quarter of the CUs),
-            // rows parked at >= 1,200 level-1 states (or >= 400 level-2 states, before that level is expanded); up to ~20 k rows 32 wide
-            // workgroups and 1,600 level-1 states; beyond that a launch keeps all CUs for mj_k_sp (sp_wide_max_rows).  The root level is never
-            // parked (nothing is known yet), level 0 is not expanded.
-            sp.promo_min[0] = sp.promo_min[3] = 1 << 30;
-            sp.promo_min[1] = P->sp_promo_min[1] > 0 ? P->sp_promo_min[1] : n <= 12000 ? 1200 : 1600;
-            sp.promo_min[2] = P->sp_promo_min[2] > 0 ? P->sp_promo_min[2] : n <= 12000 ? 400 : 1 << 30;
-            sp.n_narrow = grid;
-            sp.sweep = 0;
-            // queue order: rows counting-sorted by cost class, heaviest first (inside the timed mj_k_sp region)
-            hipLaunchKernelGGL(mj_k_order_classify, dim3((n + 255) / 256), dim3(256), 0, s, P->snap, sp.rows, n, P->sp_cls, P->sp_queue + 1);
-            hipLaunchKernelGGL(mj_k_order_scatter, dim3((n + 255) / 256), dim3(256), 0, s, P->sp_cls, n, P->sp_queue + 1, P->sp_queue + 9, P->sp_order);
-            if (!hybrid) {
-                hipLaunchKernelGGL(mj_k_sp, dim3(grid), dim3(SP_THREADS), 0, s, sp);
-            } else {
-                // mj_k_sp_wide FIRST and on the caller's stream (its few workgroups take a whole CU each and must be resident before the 1,024
-                // workgroups of mj_k_sp fill the chip), mj_k_sp on the second stream behind the row order, then the sweep behind both.
-                // The emulator runs a launch to completion: there (and with MJ_SP_WIDE_SERIAL=1) the sweep alone takes the parked rows.
-                P->sp_hybrid_launches++;
-                const int wgrid = std::min(P->sp_wide_areas, P->sp_wide_grid > 0 ? P->sp_wide_grid : n <= 12000 ? 64 : 32);
-#ifdef MJ_EMU
-                const bool serial = true;
-#else
-                static const bool serial = getenv("MJ_SP_WIDE_SERIAL") != nullptr;
-#endif
-                if (serial) {
-                    if (getenv("MJ_SP_WIDE_ALL_ROWS")) {  // (tests) the wide kernel alone first: with no producer to wait for it takes EVERY row of the queue itself
-                        SpParams spw = sp;
-                        spw.n_narrow = 0;
-                        spw.work = sp.work + grid;  // (its own areas: work + n_narrow + promo_cap + block, as in the concurrent launch)
-                        hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, spw);
-                    }
-                    hipLaunchKernelGGL(mj_k_sp_promo, dim3(grid), dim3(SP_THREADS), 0, s, sp);
-                } else {
-                    HIP_OK(hipEventRecord(P->sp_ev_fork, s));
-                    hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, sp);
-                    HIP_OK(hipStreamWaitEvent(P->sp_stream2, P->sp_ev_fork, 0));
-                    hipLaunchKernelGGL(mj_k_sp_promo, dim3(grid), dim3(SP_THREADS), 0, P->sp_stream2, sp);
-                    HIP_OK(hipEventRecord(P->sp_ev_join, P->sp_stream2));
-                    HIP_OK(hipStreamWaitEvent(s, P->sp_ev_join, 0));
-                }
-                sp.sweep = 1;
-                hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, sp);
-                if (!P->sp_gaveup_host && hipHostMalloc(&P->sp_gaveup_host, sizeof(unsigned long long)) == hipSuccess) *P->sp_gaveup_host = 0ull;
-                if (P->sp_gaveup_host) HIP_OK(hipMemcpyAsync(P->sp_gaveup_host, P->sp_err + 25, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            }
-            if (sp.rowdump) {
-                std::vector<uint32_t> h((size_t)n * 12);
-                int q[SP_Q_WORDS];
-                HIP_OK(hipMemcpyAsync(h.data(), sp.rowdump, (size_t)n * 48, hipMemcpyDeviceToHost, s));
-                HIP_OK(hipMemcpyAsync(q, P->sp_queue, sizeof(q), hipMemcpyDeviceToHost, s));
-                HIP_OK(hipStreamSynchronize(s));
-                hipFree(sp.rowdump);
-                if (FILE* f = fopen(rowdump_path, "ab")) {
-                    uint32_t hdr[12] = {0xFFFFFFFFu, (uint32_t)n};
-                    for (int k = 0; k < 10; k++) hdr[2 + k] = 0;
-                    unsigned long long tt[4];
-                    HIP_OK(hipMemcpy(tt, P->sp_err + 28, sizeof tt, hipMemcpyDeviceToHost));
-                    for (int k = 0; k < 4; k++) hdr[2 + k] = (uint32_t)tt[k];  // first workgroup in, last narrow / wide out of the row loop, end of the tail
-                    fwrite(hdr, 4, 12, f);
-                    uint32_t cc[12];
-                    for (int k = 0; k < 12; k++) cc[k] = k < 8 ? (uint32_t)q[1 + k] : 0u;
-                    fwrite(cc, 4, 12, f);
-                    for (int i = 0; i < n; i++)
-                        if (h[(size_t)i * 12 + 7]) fwrite(&h[(size_t)i * 12], 4, 12, f);
-                    fclose(f);
-                }
-            }
-        }
-        if (P->timing) {
-            HIP_OK(hipEventRecord(s1, s));
-            P->sp_events.push_back({s0, s1});
-        }
-        HIP_OK(hipGetLastError());
-    }
+    if (ep.version != 4) return 0;
+    // SP block, rows 889..1011: one decision row per persistent workgroup (mj_sp.hip: mj_k_sp; the per-phase pipeline of round 4 that
+    // lost to it: DESIGN.md section 6)
+    if (!P->sp.work && sp_setup(P, agent, obs, s)) return -1;
+    if (P->timing && P->sp_timer.begin(s)) return -1;
+    if (sp_launch(P, agent, obs, n, s)) return -1;
+    if (P->timing && P->sp_timer.end(s)) return -1;
+    HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -932,40 +1002,14 @@ int mj_encode_oracle(MjPool* P, int agent, float* out, void* stream) {
 
 int mj_encode_timing(MjPool* P, int enable, double* total_ms, int64_t* launches) {
     if (!P) return fail("null pool");
-    for (auto& e : P->events) {
-        hipEventSynchronize(e.second);
-        float ms = 0;
-        hipEventElapsedTime(&ms, e.first, e.second);
-        P->timed_ms += ms;
-        P->timed_launches += 1;
-        hipEventDestroy(e.first);
-        hipEventDestroy(e.second);
-    }
-    P->events.clear();
-    if (total_ms) *total_ms = P->timed_ms;
-    if (launches) *launches = P->timed_launches;
-    P->timed_ms = 0;
-    P->timed_launches = 0;
+    P->enc_timer.collect(total_ms, launches);
     P->timing = enable != 0;
     return 0;
 }
 
 int mj_sp_timing(MjPool* P, double* total_ms, int64_t* launches) {
     if (!P) return fail("null pool");
-    double tot = 0;
-    int64_t n = 0;
-    for (auto& e : P->sp_events) {
-        hipEventSynchronize(e.second);
-        float ms = 0;
-        hipEventElapsedTime(&ms, e.first, e.second);
-        tot += ms;
-        n += 1;
-        hipEventDestroy(e.first);
-        hipEventDestroy(e.second);
-    }
-    P->sp_events.clear();
-    if (total_ms) *total_ms = tot;
-    if (launches) *launches = n;
+    P->sp_timer.collect(total_ms, launches);
     return 0;
 }
 
@@ -1014,21 +1058,23 @@ int mj_counters(MjPool* P, uint64_t out[8], void* stream) {
     HIP_OK(hipMemcpy(tmp, P->counters, sizeof tmp, hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; i++) out[i] = tmp[i];
     out[5] = P->cycles;
-    if (P->enc_flag) {
-        int f = 0;
-        HIP_OK(hipMemcpy(&f, P->enc_flag, sizeof f, hipMemcpyDeviceToHost));
-        out[6] = (unsigned long long)f;  // (the SP block's overflows are added below)
-    }
-    if (P->sp_err) {
-        unsigned long long e2[32];
-        HIP_OK(hipMemcpy(e2, P->sp_err, sizeof e2, hipMemcpyDeviceToHost));
-        out[6] += e2[0];
-        out[7] = e2[1];
-        if (getenv("MJ_SP_PROF"))
+    int f = 0;
+    HIP_OK(hipMemcpy(&f, P->enc_flag, sizeof f, hipMemcpyDeviceToHost));
+    out[6] = (unsigned long long)f;  // (the SP block's overflows are added below)
+    if (P->sp.err) {
+        unsigned long long e2[SP_ERR_WORDS];
+        HIP_OK(hipMemcpy(e2, P->sp.err, sizeof e2, hipMemcpyDeviceToHost));
+        out[6] += e2[SP_ERR_OVERFLOW];
+        out[7] = e2[SP_ERR_ROWS];
+        const unsigned long long* pass = e2 + SP_ERR_PASS;  // (seven words: SpCtx::pt[0..6])
+        if (P->knobs.sp_prof)
             fprintf(stderr, "[sp prof] rows %llu setup %llu expand %llu evalL0 %llu evalL>0 %llu encode %llu states %llu (wall_clock64 ticks, 100 MHz) | "
                     "expand passes: probes %llu lists+V %llu td-probes %llu layout %llu inserts %llu; items %llu expanded %llu edges %llu l0-entries %llu; level-0 probe %llu scoring %llu; workgroup lifetimes: sum %llu max %llu queue pops %llu hash resets %llu; eval wavefront time %llu; shader clock %.0f MHz (s_memtime cycles %llu over the lifetimes)\n",
-                    e2[1], e2[2], e2[3], e2[4], e2[5], e2[6], e2[7], e2[8], e2[9], e2[10], e2[11], e2[12], e2[13], e2[14], e2[15], e2[16], e2[17], e2[18], e2[19], e2[20], e2[21], e2[22], e2[23],
-                    e2[19] ? 100.0 * (double)e2[24] / (double)e2[19] : 0.0, e2[24]);
+                    e2[SP_ERR_ROWS], e2[SP_ERR_T_SETUP], e2[SP_ERR_T_EXPAND], e2[SP_ERR_T_EVAL0], e2[SP_ERR_T_EVAL], e2[SP_ERR_T_WRITE], e2[SP_ERR_STATES],
+                    pass[0], pass[1], pass[2], pass[3], pass[4], pass[5], pass[6], e2[SP_ERR_EDGES], e2[SP_ERR_L0_ITEMS],
+                    e2[SP_ERR_T_L0_PROBE], e2[SP_ERR_T_L0_SCORE], e2[SP_ERR_WG_LIFE], e2[SP_ERR_WG_LIFE_MAX], e2[SP_ERR_T_POP], e2[SP_ERR_T_RESET],
+                    e2[SP_ERR_T_EVAL_WAVE], e2[SP_ERR_WG_LIFE] ? 100.0 * (double)e2[SP_ERR_WG_CLOCK] / (double)e2[SP_ERR_WG_LIFE] : 0.0,
+                    e2[SP_ERR_WG_CLOCK]);
     }
     return 0;
 }
@@ -1036,17 +1082,17 @@ int mj_counters(MjPool* P, uint64_t out[8], void* stream) {
 int mj_sp_phase_ticks(MjPool* P, uint64_t out[8], void* stream) {
     if (!P) return fail("null pool");
     for (int i = 0; i < 8; i++) out[i] = 0;
-    if (!P->sp_err) return 0;  // no obs-v4 encode has run yet
+    if (!P->sp.err) return 0;  // no obs-v4 encode has run yet
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    unsigned long long e2[8];
-    HIP_OK(hipMemcpy(e2, P->sp_err, sizeof e2, hipMemcpyDeviceToHost));
+    unsigned long long e2[8];  // SP_ERR_OVERFLOW .. SP_ERR_STATES
+    HIP_OK(hipMemcpy(e2, P->sp.err, sizeof e2, hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; i++) out[i] = e2[i];
     return 0;
 }
 
 int mj_pool_set_sp_schedule(MjPool* P, int mode, int max_rows, int wide_grid, int min_level1, int min_level2) {
     if (!P) return fail("null pool");
-    if (P->sp_work && mode != 0 && mode >= -1 && P->sp_spare == 0) return fail("mj_pool_set_sp_schedule: the work areas are allocated (call it before the first obs-v4 mj_encode)");
+    if (P->sp.work && mode != 0 && mode >= -1 && P->sp.spare == 0) return fail("mj_pool_set_sp_schedule: the work areas are allocated (call it before the first obs-v4 mj_encode)");
     if (mode >= -1) P->sp_wide_mode = mode > 0 ? 1 : mode;
     if (max_rows > 0) P->sp_wide_max_rows = max_rows;
     if (wide_grid > 0) P->sp_wide_grid = std::min(wide_grid, 256);
@@ -1059,14 +1105,14 @@ int mj_pool_set_sp_schedule(MjPool* P, int mode, int max_rows, int wide_grid, in
 int mj_sp_schedule_stats(MjPool* P, uint64_t out[4], void* stream) {
     if (!P) return fail("null pool");
     for (int i = 0; i < 4; i++) out[i] = 0;
-    if (!P->sp_err) return 0;
+    if (!P->sp.err) return 0;
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    unsigned long long e2[32];
-    HIP_OK(hipMemcpy(e2, P->sp_err, sizeof e2, hipMemcpyDeviceToHost));
+    unsigned long long e2[SP_ERR_WORDS];
+    HIP_OK(hipMemcpy(e2, P->sp.err, sizeof e2, hipMemcpyDeviceToHost));
     out[0] = P->sp_hybrid_launches;
-    out[1] = e2[26];
-    out[2] = e2[27];
-    out[3] = e2[25];
+    out[1] = e2[SP_ERR_PROMOTED];
+    out[2] = e2[SP_ERR_SWEPT];
+    out[3] = e2[SP_ERR_WIDE_GAVEUP];
     return 0;
 }
 

@@ -169,13 +169,46 @@ struct SpParams {
                                // [9..16] class cursors of the row sort, [SP_Q_TAIL] head of the queue's tail (rows without a graph)
     const uint32_t* order;     // [n_rows] queue position -> row index, heaviest cost class first (mj_k_order_classify / _scatter)
     unsigned long long* prof;  // NULL or [24] phase timers / counters (MJ_SP_PROF; mj_counters prints them)
-    unsigned long long* err;   // [0] hash-capacity overflows, [1] rows; cycle sums: [2] setup [3] expand [4] eval L0 [5] eval L>0 [6] encode; [7] states
+    unsigned long long* err;   // [SP_ERR_WORDS] counter words (SpErrWord below)
     uint32_t* rowdump;         // (builds with -DSP_ROWDUMP only: tools/build_variant.sh dump -DSP_ROWDUMP) NULL, or [n_rows][12] per-row records of the rows with a state graph (MJ_SP_ROWDUMP: cost-model data for the row order)
     // promotion of large rows to mj_k_sp_wide (small pools; see "promotion" at mj_k_sp)
     int promo_cap;             // spare work areas = promotions allowed in this launch (0: off); work[] holds grid + promo_cap areas
     int promo_min[4];          // [level]: park the row when the level about to be expanded has at least this many states
     int n_narrow;              // mj_k_sp_wide: workgroups of mj_k_sp in this launch (the DONE word's final value)
     int sweep;                 // mj_k_sp_wide: 1 = the sweep launch behind both kernels (never waits)
+};
+
+// The words of SpParams::err (cumulative over the pool's launches; read by mj_counters, mj_sp_phase_ticks, mj_sp_schedule_stats).
+// Ticks are wall_clock64 (100 MHz) summed over workgroups; the words up to SP_ERR_STATS are gathered per workgroup in LDS first.
+enum SpErrWord {
+    SP_ERR_OVERFLOW = 0,      // rows whose hash set overflowed
+    SP_ERR_ROWS = 1,          // rows written
+    SP_ERR_T_SETUP = 2,       // phase ticks: row set-up (+ the whole of a row without a state graph)
+    SP_ERR_T_EXPAND = 3,      //   expansion
+    SP_ERR_T_EVAL0 = 4,       //   level 0 (probe + scoring + sum)
+    SP_ERR_T_EVAL = 5,        //   evaluation of levels > 0
+    SP_ERR_T_WRITE = 6,       //   writing the row
+    SP_ERR_STATES = 7,        // states visited
+    SP_ERR_PASS = 8,          // [8..14] expansion pass timers / counters (SpCtx::pt[0..6], MJ_SP_PROF)
+    SP_ERR_EDGES = 15,        // child-list entries (edges of the state graphs)
+    SP_ERR_L0_ITEMS = 16,     // level-0 draw entries scored
+    SP_ERR_T_L0_PROBE = 17,   // level-0 probe ticks (SpCtx::pt[7], MJ_SP_PROF)
+    SP_ERR_T_L0_SCORE = 18,   // level-0 scoring ticks (MJ_SP_PROF)
+    SP_ERR_WG_LIFE = 19,      // workgroup lifetimes: sum (MJ_SP_PROF) ...
+    SP_ERR_WG_LIFE_MAX = 20,  // ... max
+    SP_ERR_T_POP = 21,        // queue pops
+    SP_ERR_T_RESET = 22,      // hash resets
+    SP_ERR_T_EVAL_WAVE = 23,  // wavefront time inside the evaluation (all levels)
+    SP_ERR_WG_CLOCK = 24,     // shader-clock cycles (s_memtime) over the lifetimes: / SP_ERR_WG_LIFE x 100 MHz = the kernel's clock
+    SP_ERR_STATS = 25,        // (the words gathered per workgroup: 0 .. 24)
+    SP_ERR_WIDE_GAVEUP = 25,  // wide workgroups that gave up waiting (the two kernels did not overlap)
+    SP_ERR_PROMOTED = 26,     // rows parked and finished by mj_k_sp_wide
+    SP_ERR_SWEPT = 27,        // rows the sweep launch had to take
+    SP_ERR_DUMP_T0 = 28,      // (-DSP_ROWDUMP) first workgroup start of the graph-row loops,
+    SP_ERR_DUMP_NARROW = 29,  //   last narrow / ...
+    SP_ERR_DUMP_WIDE = 30,    //   ... wide workgroup out of them,
+    SP_ERR_DUMP_TAIL = 31,    //   end of the queue's tail
+    SP_ERR_WORDS = 32
 };
 
 // algo/data/uradora_prob_table.txt (values restated; calc.rs:17)
@@ -2092,8 +2125,8 @@ template <int NT, bool WIDE, bool PROMO>
 __device__ __forceinline__ void sp_kernel_body(SpParams P) {
     __shared__ SpCtx X;
     __shared__ int s_row, s_k;
-    __shared__ unsigned long long s_stat[25];  // this workgroup's share of SpParams::err, flushed once (see sp_light_row)
-    if (threadIdx.x < 25) s_stat[threadIdx.x] = 0ull;
+    __shared__ unsigned long long s_stat[SP_ERR_STATS];  // this workgroup's share of SpParams::err, flushed once (see sp_light_row)
+    if (threadIdx.x < SP_ERR_STATS) s_stat[threadIdx.x] = 0ull;
     __shared__ typename SpLds<NT>::Teams s_tm;
 #if SP_CC_N > 0
     __shared__ unsigned long long s_cc[SP_CC_N];  // the child cache of the expansion (sp_expand_chunk)
@@ -2111,9 +2144,9 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
     bool main_done = false, drained = false;  // (mj_k_sp_wide, lane 0: the row queue is empty; the last look at the promotion queues)
 
     const long long t_wg_in = SP_DUMP(P) ? wall_clock64() : 0;
-    const long long t_wg0 = P.prof ? wall_clock64() : 0;  // MJ_SP_PROF: workgroup lifetime / queue + reset time (err[19..22])
+    const long long t_wg0 = P.prof ? wall_clock64() : 0;  // MJ_SP_PROF: workgroup lifetime / queue + reset time (SP_ERR_WG_LIFE .. SP_ERR_T_RESET)
 #ifndef MJ_EMU
-    const long long c_wg0 = P.prof ? clock64() : 0;       // the same lifetime in shader-clock cycles (s_memtime): err[24] / err[19] x 100 MHz = the clock the kernel ran at
+    const long long c_wg0 = P.prof ? clock64() : 0;       // the same lifetime in shader-clock cycles (s_memtime, SP_ERR_WG_CLOCK)
 #endif
     long long t_pop = 0, t_reset = 0;
     // the queue is ordered by cost class (mj_k_order_*): the rows of class 7 (no state graph at all) form its tail
@@ -2148,7 +2181,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                             while ((e = __hip_atomic_load(ents + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0 && !P.sweep &&
                                    wall_clock64() - t_w < SP_WIDE_TIMEOUT)
                                 SP_SPIN_PAUSE();
-                            if (e == 0 && !P.sweep) atomicAdd(&P.err[25], 1ull);  // (left to the sweep)
+                            if (e == 0 && !P.sweep) atomicAdd(&P.err[SP_ERR_WIDE_GAVEUP], 1ull);  // (left to the sweep)
                             if (e > 0 && atomicCAS(ents + h, e, -1) == e) {       // (the sweep skips what the first launch took)
                                 got = e;
                                 break;
@@ -2174,7 +2207,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                     const long long now = wall_clock64();
                     if (t_idle == 0) t_idle = now;
                     else if (now - t_idle > SP_WIDE_TIMEOUT) {  // the two kernels do not overlap (or mj_k_sp has not started): give up, the sweep follows
-                        atomicAdd(&P.err[25], 1ull);
+                        atomicAdd(&P.err[SP_ERR_WIDE_GAVEUP], 1ull);
                         break;
                     }
                     SP_SPIN_PAUSE();
@@ -2188,7 +2221,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
             t_0 = wall_clock64();
             if (s_row > 0) {
                 promoted = true;
-                if (tid == 0) atomicAdd(&P.err[P.sweep ? 27 : 26], 1ull);  // rows finished here (by the sweep launch: the two kernels did not overlap)
+                if (tid == 0) atomicAdd(&P.err[P.sweep ? SP_ERR_SWEPT : SP_ERR_PROMOTED], 1ull);  // rows finished here (by the sweep launch: the two kernels did not overlap)
                 W = P.work + (s_row - 1);
                 SP_HBM const u32* src = (SP_HBM const u32*)W->handoff;
                 u32* dx = reinterpret_cast<u32*>(&X);
@@ -2343,7 +2376,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                     __syncthreads();
                     if (P.prof && tid == 0) {  // level-0 sub-phases: probe, scoring (the sum is the rest of the level-0 timer)
                         X.pt[7] += (unsigned long long)(t_2a - t_2);
-                        s_stat[18] += (unsigned long long)(wall_clock64() - t_2a);
+                        s_stat[SP_ERR_T_L0_SCORE] += (unsigned long long)(wall_clock64() - t_2a);
                     }
                 }
                 sp_sort_level<NT>(W, reinterpret_cast<int*>(s_tm.ev), b, e);
@@ -2379,7 +2412,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                             else sp_eval_wave<17, 2>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
                         }
                     }
-                    if (P.prof && (tid & 63) == 0) atomicAdd(&s_stat[23], (unsigned long long)(wall_clock64() - t_ev0));  // wavefront time inside the evaluation (all levels)
+                    if (P.prof && (tid & 63) == 0) atomicAdd(&s_stat[SP_ERR_T_EVAL_WAVE], (unsigned long long)(wall_clock64() - t_ev0));  // wavefront time inside the evaluation (all levels)
                 }
                 __syncthreads();
                 if (lv == 0) t_3 = wall_clock64();
@@ -2391,21 +2424,21 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         __syncthreads();
         if (tid == 0) {
             long long t_5 = wall_clock64();
-            if (!parked) s_stat[1] += 1ull;
-            s_stat[2] += (unsigned long long)(t_1 - t_0);
+            if (!parked) s_stat[SP_ERR_ROWS] += 1ull;
+            s_stat[SP_ERR_T_SETUP] += (unsigned long long)(t_1 - t_0);
             if (with_probs) {
-                s_stat[3] += (unsigned long long)(t_2 - t_1);
+                s_stat[SP_ERR_T_EXPAND] += (unsigned long long)(t_2 - t_1);
                 if (!parked) {
-                    s_stat[4] += (unsigned long long)(t_3 - t_2);
-                    s_stat[5] += (unsigned long long)(t_4 - t_3);
-                    s_stat[6] += (unsigned long long)(t_5 - t_4);
-                    s_stat[7] += (unsigned long long)X.n_list;
-                    s_stat[15] += (unsigned long long)X.n_pool;   // child-list entries (edges of the state graph)
-                    s_stat[16] += (unsigned long long)X.n_items;  // level-0 draw entries scored
+                    s_stat[SP_ERR_T_EVAL0] += (unsigned long long)(t_3 - t_2);
+                    s_stat[SP_ERR_T_EVAL] += (unsigned long long)(t_4 - t_3);
+                    s_stat[SP_ERR_T_WRITE] += (unsigned long long)(t_5 - t_4);
+                    s_stat[SP_ERR_STATES] += (unsigned long long)X.n_list;
+                    s_stat[SP_ERR_EDGES] += (unsigned long long)X.n_pool;
+                    s_stat[SP_ERR_L0_ITEMS] += (unsigned long long)X.n_items;
                 }
                 if (P.prof)
-                    for (int k = 0; k < 7; k++) s_stat[8 + k] += X.pt[k];  // expansion pass timers (MJ_SP_PROF)
-                if (P.prof) s_stat[17] += X.pt[7];                          // level-0 probe
+                    for (int k = 0; k < 7; k++) s_stat[SP_ERR_PASS + k] += X.pt[k];
+                if (P.prof) s_stat[SP_ERR_T_L0_PROBE] += X.pt[7];
             }
             if (SP_DUMP(P) && !parked) {  // (debug) queue position | wide << 31, shanten | T << 8 | n_cand << 16 | can_discard << 24, sum of the candidates' required kinds, states, edges, l0 items, ticks, level sizes
                 uint32_t* d = P.rowdump + (size_t)row * 12;
@@ -2424,7 +2457,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         }
         // ---- the hash set needs no reset (tag epochs); a row that overflowed it is counted
         const long long t_r = P.prof ? wall_clock64() : 0;
-        if (X.overflow && tid == 0 && !parked) s_stat[0] += 1ull;
+        if (X.overflow && tid == 0 && !parked) s_stat[SP_ERR_OVERFLOW] += 1ull;
         __syncthreads();
         if (P.prof) t_reset += wall_clock64() - t_r;
     }
@@ -2442,20 +2475,20 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
     }
     if (P.prof && tid == 0) {
         const unsigned long long life = (unsigned long long)(wall_clock64() - t_wg0);
-        s_stat[19] += life;
+        s_stat[SP_ERR_WG_LIFE] += life;
 #ifndef MJ_EMU
-        s_stat[24] += (unsigned long long)(clock64() - c_wg0);
+        s_stat[SP_ERR_WG_CLOCK] += (unsigned long long)(clock64() - c_wg0);
 #endif
-        atomicMax(&P.err[20], life);
-        s_stat[21] += (unsigned long long)t_pop;
-        s_stat[22] += (unsigned long long)t_reset;
+        atomicMax(&P.err[SP_ERR_WG_LIFE_MAX], life);
+        s_stat[SP_ERR_T_POP] += (unsigned long long)t_pop;
+        s_stat[SP_ERR_T_RESET] += (unsigned long long)t_reset;
     }
     __syncthreads();  // (every thread leaves the row loop at the same pop)
     if (SP_DUMP(P) && tid == 0) {  // (debug) first workgroup start / last end of the graph-row loops, both kernels
-        atomicMin(&P.err[28], (unsigned long long)t_wg_in);
-        atomicMax(&P.err[WIDE ? 30 : 29], (unsigned long long)wall_clock64());
+        atomicMin(&P.err[SP_ERR_DUMP_T0], (unsigned long long)t_wg_in);
+        atomicMax(&P.err[WIDE ? SP_ERR_DUMP_WIDE : SP_ERR_DUMP_NARROW], (unsigned long long)wall_clock64());
     }
-    if (tid < 25 && tid != 20 && s_stat[tid]) atomicAdd(&P.err[tid], s_stat[tid]);  // the workgroup's statistics, once
+    if (tid < SP_ERR_STATS && tid != SP_ERR_WG_LIFE_MAX && s_stat[tid]) atomicAdd(&P.err[tid], s_stat[tid]);  // the workgroup's statistics, once
     // ---- the tail of the queue: every wavefront takes its own rows (set-up + encoder only, no workgroup barrier any more)
     // The tail has its own head word (another 128-byte line than the heavy rows' head) and is popped SP_TAIL_BATCH rows at a time:
     // ~46 k light rows per launch against 4,096 wavefronts that need ~10 us per row ask for ~400 pops per microsecond, and one word
@@ -2478,11 +2511,11 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
             }
         }
         if (lane == 0 && w_rows) {  // the wavefront's statistics, once
-            atomicAdd(&P.err[1], w_rows);
-            atomicAdd(&P.err[2], w_ticks);
-            if (w_over) atomicAdd(&P.err[0], w_over);
+            atomicAdd(&P.err[SP_ERR_ROWS], w_rows);
+            atomicAdd(&P.err[SP_ERR_T_SETUP], w_ticks);
+            if (w_over) atomicAdd(&P.err[SP_ERR_OVERFLOW], w_over);
         }
-        if (SP_DUMP(P) && lane == 0) atomicMax(&P.err[31], (unsigned long long)wall_clock64());  // (debug) end of the tail
+        if (SP_DUMP(P) && lane == 0) atomicMax(&P.err[SP_ERR_DUMP_TAIL], (unsigned long long)wall_clock64());  // (debug) end of the tail
     }
     }
 }

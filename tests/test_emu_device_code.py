@@ -281,3 +281,34 @@ def test_emu_sp_schedule_api(emu):
         pool.set_sp_schedule(mode=1)
     pool.set_sp_schedule(min_level1=900, min_level2=300)  # (allowed: only mode needs the areas)
     pool.close()
+
+
+def test_emu_encode_and_sp_timing_count_every_timed_launch(emu):
+    """mj_encode_timing / mj_sp_timing: with timing on, every non-empty obs-v4 encode is one timed encoder launch and one timed SP
+    launch; reading the totals hands the pool's event pairs back, so a second timed round on the same pool counts the same way."""
+    import numpy as np
+
+    pool = emu(4, version=4)
+    pool.reset(parity_util.default_seeds(4), game_ids=np.arange(4), n_games_total=4)
+    act, c = None, 0
+
+    def cycles(k):
+        nonlocal act, c
+        encodes = 0
+        for _ in range(k):
+            n, _ = pool.step(act, None)
+            obs, masks = pool.encode(0)
+            encodes += n > 0
+            act = pool.random_policy(0, masks, 3, c)
+            c += 1
+        return encodes
+
+    for _ in range(2):
+        pool.encode_timing(True)
+        encodes = cycles(10)
+        _, launches = pool.encode_timing(False)
+        _, sp_launches = pool.sp_timing()
+        assert encodes > 0 and launches == encodes and sp_launches == encodes, (encodes, launches, sp_launches)
+        assert pool.sp_timing()[1] == 0
+        cycles(3)  # (timing off: nothing recorded)
+    pool.close()
