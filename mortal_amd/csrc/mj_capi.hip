@@ -1079,6 +1079,11 @@ int mj_counters(MjPool* P, uint64_t out[8], void* stream) {
     return 0;
 }
 
+#ifdef MJ_EMU
+// emulator builds only (not part of the C-ABI): states placed in mj_k_sp's LDS set / in the HBM table since the library was loaded
+void mj_emu_sp_placed(uint64_t out[2]) { out[0] = g_sp_emu_placed[0]; out[1] = g_sp_emu_placed[1]; }
+#endif
+
 int mj_sp_phase_ticks(MjPool* P, uint64_t out[8], void* stream) {
     if (!P) return fail("null pool");
     for (int i = 0; i < 8; i++) out[i] = 0;

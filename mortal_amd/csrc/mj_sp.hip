@@ -56,11 +56,17 @@
 #endif
 #define SP_WGS (4 * SP_WPS * 64 / SP_THREADS)  // resident workgroups per CU
 
-#ifndef SP_CC_N
-#define SP_CC_N 2048            // entries of the per-workgroup child cache in LDS (0 = off): row epoch << 56 | state id << 14 | slot.
-                                // Measured (round 4, one box, mj_k_sp): none 20.01 ms, 512: 19.78, 1024: 19.73-19.77, 2048: 19.61 (16 KB: with the
-                                // rest 40.8 KB per workgroup, the last size that keeps four workgroups on a CU)
+#ifndef SP_SET_BUCKETS
+#define SP_SET_BUCKETS 1024     // buckets (two 8-byte ways each, one ds_read_b128) of the per-workgroup table in LDS.  mj_k_sp: the FIRST part of
+                                // the row's hash set (sp_set_find_or_claim; a state that finds its four ways taken lives in SpWork::tag).
+                                // mj_k_sp_promo / mj_k_sp_wide, whose rows change workgroups mid-graph: a direct-mapped cache (id -> slot) of
+                                // as many entries in front of SpWork::tag (rounds 4-6 in all three kernels; round 4, mj_k_sp: none 20.01 ms,
+                                // 512 entries 19.78, 2048: 19.61).  16 KB: with the rest 40.8 KB per workgroup, the last size that keeps
+                                // four workgroups on a CU.  Tests build tiny ones (most states overflow to HBM).
 #endif
+#define SP_SET_SLOTS (2 * SP_SET_BUCKETS)  // node slots [0, SP_SET_SLOTS) = the ways of the LDS set; a state of the HBM table: SP_SET_SLOTS + position
+#define SP_NODES (SP_CAP + SP_SET_SLOTS)
+static_assert((SP_SET_BUCKETS & (SP_SET_BUCKETS - 1)) == 0 && SP_SET_BUCKETS >= 1 && SP_NODES <= (1 << 15), "slots are 15-bit fields");
 #ifndef SP_TAIL_BATCH
 #define SP_TAIL_BATCH 4         // rows per pop in the tail of the queue (rows without a state graph, one row per wavefront)
 #endif
@@ -82,8 +88,8 @@
 #define SP_POOL (SP_CAP * 32)   // child-list pool entries per workgroup
 #define SP_ITEMS (SP_CAP * 4)   // level-0 scoring items per workgroup
 #define SP_L0_MAX 17            // winning draw entries per tenpai state (13 waits + 3 aka variants)
-#define SP_EL_SLOT(v) ((v) & (SP_CAP - 1))  // an elist entry: hash slot | list index << 14
-#define SP_EL_IDX(v) ((v) >> 14)
+#define SP_EL_SLOT(v) ((v) & 0x7FFFu)  // an elist entry: slot (15 bits) | list index << 15
+#define SP_EL_IDX(v) ((v) >> 15)
 struct alignas(128) SpNode {    // one 3n+1 state's VALUES: 256 bytes = exactly two 128-byte lines, addressed by hash slot (round 5;
                                 // rounds 1-4: 608 bytes with the state's key, header and level-0 scores inside, 16-byte value rows).
                                 // A parent reads val[] of its children, ~6 parents per child: those reads are what the evaluation
@@ -106,22 +112,22 @@ struct SpKeys {                 // a state's key and exact id, DENSE by list ind
     u64 k0, k1, k2, k3;         // hand.mp | hand.sz + akas_in_hand<<48 | wall.mp | wall.sz + akas_in_wall<<48
     u64 dk;                     // state id (sp_dk_add)
 };
-// A child-list entry: hash slot of the child | discard order key << 14 | last-discard-of-its-draw-entry << 23 |
-// draw count << 24 | invalid (hash set overflow) << 27.  Order: draw tile ascending, plain before red, discard ascending.
-#define SP_ENT_SLOT(e) ((e) & 0x3FFFu)
-#define SP_ENT_KEY(e) (((e) >> 14) & 511u)
-#define SP_ENT_LAST (1u << 23)
-#define SP_ENT_COUNT(e) (((e) >> 24) & 7u)
-#define SP_ENT_INVALID (1u << 27)
+// A child-list entry: slot of the child (15 bits) | discard order key << 15 | last-discard-of-its-draw-entry << 24 |
+// draw count << 25 | invalid (hash set overflow) << 28.  Order: draw tile ascending, plain before red, discard ascending.
+#define SP_ENT_SLOT(e) ((e) & 0x7FFFu)
+#define SP_ENT_KEY(e) (((e) >> 15) & 511u)
+#define SP_ENT_LAST (1u << 24)
+#define SP_ENT_COUNT(e) (((e) >> 25) & 7u)
+#define SP_ENT_INVALID (1u << 28)
 struct alignas(16) SpF4 { float x, y, z, w; };
 #define SP_HANDOFF_WORDS 1024   // >= sizeof(SpHandoff) / 4 (static_assert below)
-struct alignas(128) SpWork {   // per-workgroup scratch in HBM (persistent workgroups), 8.1 MB
+struct alignas(128) SpWork {   // per-workgroup scratch in HBM (persistent workgroups), 8.6 MB
     u64 tag[SP_CAP];           // state id | row epoch << 42 | 1 << 63; a tag of another epoch (or 0) is an EMPTY slot
-    SpNode node[SP_CAP];       // by hash slot
+    SpNode node[SP_NODES];     // by slot: [0, SP_SET_SLOTS) the ways of the LDS set (mj_k_sp), SP_SET_SLOTS + position in tag[]
     SpKeys keys[SP_CAP];       // by list index
     SpHdr hdr[SP_CAP];         // by list index
     u32 list[SP_CAP];          // slots grouped by level: level L occupies [lvl_begin[L], lvl_end[L])
-    u32 elist[SP_CAP];         // the same ranges ordered by child-list length for the evaluation (sp_sort_level): slot | list index << 14
+    u32 elist[SP_CAP];         // the same ranges ordered by child-list length for the evaluation (sp_sort_level): slot | list index << 15
     u32 pool[SP_POOL];         // child lists
     u32 items[SP_ITEMS];       // level 0: (list index, winning tile, variant) work items of the dense scoring pass
     SpF4 l0sc[SP_ITEMS];       // level 0: get_score() of every work item (sp_l0_score), all zero = no yaku
@@ -129,7 +135,7 @@ struct alignas(128) SpWork {   // per-workgroup scratch in HBM (persistent workg
     u32 pad_[31];
     alignas(16) u32 handoff[SP_HANDOFF_WORDS];  // a promoted row's context (SpHandoff: SpCtx + SpRowInfo + row + next level), written by its first workgroup
 #ifdef MJ_EMU
-    u32 idx_of[SP_CAP];        // emulator only: slot -> list index, for the id <-> key bijection check on every hit
+    u32 idx_of[SP_NODES];      // emulator only: slot -> list index, for the id <-> key bijection check on every hit
 #endif
 };
 static_assert(offsetof(SpWork, node) % 128 == 0 && sizeof(SpWork) % 128 == 0, "nodes on line boundaries");
@@ -277,8 +283,8 @@ struct alignas(16) SpCtx {  // per-decision constants (LDS)
     int overflow;
     unsigned long long* prof;  // optional phase timers (MJ_SP_PROF)
     unsigned long long pt[8];  // per-row sums of the expansion pass timers / counters (flushed once per row)
-    unsigned long long* cc;    // the workgroup's child cache in LDS (SP_CC_N entries; NULL: none) and this row's epoch (8 bits, never 0... see mj_k_sp)
-    unsigned cc_epoch;
+    u64* set;                  // the workgroup's table in LDS (SP_SET_SLOTS entries): mj_k_sp's hash set, the child cache of the other two
+    unsigned cc_epoch;         // (child cache) this row's epoch (8 bits, never 0... see sp_kernel_body)
     unsigned tag_epoch;        // this row's epoch in the hash tags (sp_tag_free)
     // candidates
     int n_cand;
@@ -390,12 +396,19 @@ MJD u64 sp_dk_add(u64 dk, int draw_tile, int discard_tile) {  // -1 = none
     }
     return (u64)(d0 | (d1 << 6) | (d2 << 12) | (x0 << 18) | (x1 << 24)) | ((u64)(x2 | (x3 << 6)) << 30);
 }
-MJD u32 sp_dk_pos(u64 dk) {  // first probe position
+MJD u32 sp_dk_hash(u64 dk) {  // 32 mixed bits of the id: the top 14 are the HBM table's first probe position, two fields below the LDS buckets
     u32 h = (u32)dk * 0x9E3779B1u ^ ((u32)(dk >> 32) + 0x7F4A7C15u) * 0x85EBCA77u;
     h ^= h >> 15;
-    return (h * 0x2C1B3C6Du) >> 18;  // top 14 bits: SP_CAP slots
+    return h * 0x2C1B3C6Du;
 }
-static_assert(SP_CAP == 1 << 14, "sp_dk_pos returns 14 bits");
+MJD u32 sp_hash_pos(u32 h) { return h >> 18; }  // top 14 bits: SP_CAP slots
+MJD u32 sp_dk_pos(u64 dk) { return sp_hash_pos(sp_dk_hash(dk)); }
+static_assert(SP_CAP == 1 << 14, "sp_hash_pos returns 14 bits");
+// The two buckets of the LDS set: two disjoint bit fields of the hash (the second one overlaps the HBM position, which is no choice of
+// this table's).  Equal buckets are harmless: the same two ways are tried twice.
+MJD u32 sp_hash_b1(u32 h) { return (h >> 8) & (SP_SET_BUCKETS - 1); }
+MJD u32 sp_hash_b2(u32 h) { return (h >> 18) & (SP_SET_BUCKETS - 1); }
+static_assert(SP_SET_BUCKETS <= 1024, "two disjoint 10-bit fields of the hash");
 // Tags carry the EPOCH of the row that set them (21 bits between the 42-bit id and the valid bit): a slot whose tag belongs to another
 // row is empty, so nothing has to be cleared between rows (rounds 1-4: one 8-byte store per state, 0.7 GB per launch as 32-byte
 // sectors, after re-reading the list).  The epoch counts this workgroup's graph rows (SpWork::epoch, kept across launches); when
@@ -481,32 +494,79 @@ __device__ __forceinline__ void sp_new_state(WP W, SpCtx* X, u32 slot, u64 dk, c
         X->overflow = 1;
     }
 }
-#ifdef MJ_EMU  // the emulator never pre-empts between the claim and the key write: check the bijection on every hit
+#ifdef MJ_EMU  // check the id <-> key bijection on every hit.  A way of the LDS set is claimed a collective before its state gets its record
+               // (sp_expand_chunk), so a hit may find the slot's index stale: then it names another id and there is nothing to compare
 template <class WP>
-inline void sp_emu_check_hit(WP W, SpCtx* X, u32 slot, const SpState& st) {
+inline void sp_emu_check_hit(WP W, SpCtx* X, u32 slot, u64 dk, const SpState& st) {
     u64 k[4];
     sp_key(st, k);
-    const auto& e = W->keys[W->idx_of[slot]];
-    if (e.k0 != k[0] || e.k1 != k[1] || e.k2 != k[2] || e.k3 != k[3]) X->overflow = 1;
+    const u32 idx = W->idx_of[slot];
+    if (idx >= (u32)SP_CAP) return;
+    const auto& e = W->keys[idx];
+    if (e.dk == dk && (e.k0 != k[0] || e.k1 != k[1] || e.k2 != k[2] || e.k3 != k[3])) X->overflow = 1;
 }
+inline unsigned long long g_sp_emu_placed[2];  // states placed in the LDS set / in the HBM table (tests: a small set must send states both ways)
 #endif
-template <class WP>
+// The LDS part of the hash set (mj_k_sp): SP_SET_BUCKETS buckets of two ways, each way a tag as in SpWork::tag (a tag of another epoch
+// is a free way; nothing is cleared between rows).  A state has two buckets; both are read (one ds_read_b128 each, issued together)
+// before either is looked at.  It lives in the FIRST way free of this row's states in the fixed order bucket 1 way 0, way 1, bucket 2
+// way 0, way 1, claimed by compare-and-swap; a way is never freed within a row, so every lane that looks for the same id walks the same
+// ways to the same end, whenever it looks -- two lanes inserting one id in the same round meet at the same way (the loser finds the id
+// there), and a state that found all four ways taken by others (-> the HBM table) is never found or placed here later.
+// Returns the slot (2 * bucket + way) | 1 << 16 if this call claimed it (a fresh state), or -1: not in LDS, and never will be.
+__device__ __forceinline__ int sp_set_find_or_claim(u64* set, u32 h, u64 tag, u32 ep) {
+    struct alignas(16) Bucket { u64 w[2]; };
+    const u32 b[2] = {sp_hash_b1(h), sp_hash_b2(h)};
+    const Bucket B0 = reinterpret_cast<const Bucket*>(set)[b[0]], B1 = reinterpret_cast<const Bucket*>(set)[b[1]];
+    const u64 w[4] = {B0.w[0], B0.w[1], B1.w[0], B1.w[1]};
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (w[i] == tag) return (int)(2 * b[i >> 1] + (i & 1));
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (!sp_tag_free(w[i], ep)) continue;  // another state of this row: for good
+        const u32 slot = 2 * b[i >> 1] + (i & 1);
+        const u64 old = sp_claim_tag(&set[slot], tag, w[i]);
+        if (old == 0ull) return (int)slot | (1 << 16);
+        if (old == tag) return (int)slot;  // another lane has just placed this very state here
+    }
+    return -1;
+}
+template <bool LDS_SET, class WP>
 __device__ __forceinline__ int sp_insert(WP W, SpCtx* X, u64 dk, const SpState& base, int tile, int dt) {  // (the row's root states)
     const u32 ep = X->tag_epoch;
     const u64 tag = SP_TAG(dk, ep);
-    u32 pos = sp_dk_pos(dk);
+    const u32 h = sp_dk_hash(dk);
+    constexpr u32 HB = LDS_SET ? SP_SET_SLOTS : 0;  // the HBM table's first node slot
+    if constexpr (LDS_SET) {
+        u64* const set = X->set;
+        SP_ASSUME_LDS(set);
+        const int r = sp_set_find_or_claim(set, h, tag, ep);
+        if (r >= 0) {
+            if (r >> 16) sp_new_state(W, X, (u32)(r & 0xFFFF), dk, sp_apply(base, tile, dt));
+#ifdef MJ_EMU
+            if (r >> 16) g_sp_emu_placed[0]++;
+            else sp_emu_check_hit(W, X, (u32)r, dk, sp_apply(base, tile, dt));
+#endif
+            return r & 0xFFFF;
+        }
+    }
+    u32 pos = sp_hash_pos(h);
     for (int probe = 0; probe < SP_CAP; probe++) {
         u64 old = W->tag[pos];
         if (sp_tag_free(old, ep)) old = sp_claim_tag(&W->tag[pos], tag, old);
         if (old == 0ull) {
-            sp_new_state(W, X, pos, dk, sp_apply(base, tile, dt));
-            return (int)pos;
+            sp_new_state(W, X, HB + pos, dk, sp_apply(base, tile, dt));
+#ifdef MJ_EMU
+            g_sp_emu_placed[1]++;
+#endif
+            return (int)(HB + pos);
         }
         if (old == tag) {
 #ifdef MJ_EMU
-            sp_emu_check_hit(W, X, pos, sp_apply(base, tile, dt));
+            sp_emu_check_hit(W, X, HB + pos, dk, sp_apply(base, tile, dt));
 #endif
-            return (int)pos;
+            return (int)(HB + pos);
         }
         pos = (pos + 1) & (SP_CAP - 1);
     }
@@ -858,6 +918,7 @@ __device__ SP_ATTR_L0P void sp_l0_probe_chunk(SpWork* W, SpCtx* X, SpChunk* C, i
 }
 
 // Levels >= 1: required draws, shanten-keeping discards and the children of SP_NS states.
+template <bool LDS_SET>  // mj_k_sp: the first part of the hash set in LDS; the other two kernels: the child cache in front of the HBM table
 __device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, int first, int n, int L) {
     SP_ASSUME_LDS(X);
     SP_ASSUME_LDS(C);
@@ -1002,7 +1063,7 @@ __device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, 
             bool on;
             int s, it, local, rank, nk, tile, dt, count;
             u64 dk;
-            u32 pos;
+            u32 h;  // sp_dk_hash(dk)
         };
         auto decode = [&](int e) -> Ent {
             Ent E;
@@ -1051,30 +1112,38 @@ __device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, 
             else if (d == T_5S && (akas1 & 4) && c == 1) dt = T_5SR;
             E.dt = dt;
             E.dk = sp_dk_add(C->dk[E.s], E.tile, dt);
-            E.pos = sp_dk_pos(E.dk);
+            E.h = sp_dk_hash(E.dk);
             return E;
         };
+        constexpr u32 HB = LDS_SET ? SP_SET_SLOTS : 0;  // the HBM table's first node slot
+        // `known`: what LDS answered, the slot (| 1 << 16: a way of the set claimed by this call = a fresh state), or -1: the HBM table,
+        // whose first look is `first_old`
         auto finish = [&](const Ent& E, u64 first_old, int known) -> int {  // the rest of sp_insert after the first look, the list and the child entry
             const u64 tag = SP_TAG(E.dk, tag_ep);
             const SpState Sx = sp_chunk_state(C, E.s);
-            u32 pos = E.pos;
+            u32 pos = sp_hash_pos(E.h);
             u64 old = first_old;
-            int cs = known;  // >= 0: the child cache knew the slot
-            bool fresh = false;
+            int cs = known >= 0 ? (known & 0xFFFF) : -1;
+            bool fresh = known >= 0 && (known >> 16) != 0;
 #ifdef MJ_EMU
-            if (known >= 0 && Wg->tag[known] != tag) X->overflow = 1;  // a cache hit must name the slot that holds this very state
+            if (LDS_SET && known >= 0 && !fresh) sp_emu_check_hit(Wg, X, (u32)cs, E.dk, sp_apply(Sx, E.tile, E.dt));
+            if (!LDS_SET && known >= 0 && Wg->tag[known] != tag) X->overflow = 1;  // a cache hit must name the slot that holds this very state
+            if (fresh) g_sp_emu_placed[0]++;
 #endif
             for (int probe = 0; cs < 0 && probe < SP_CAP; probe++) {
                 if (old == 0ull) {
                     fresh = true;
-                    cs = (int)pos;
+                    cs = (int)(HB + pos);
+#ifdef MJ_EMU
+                    g_sp_emu_placed[1]++;
+#endif
                     break;
                 }
                 if (old == tag) {
 #ifdef MJ_EMU
-                    sp_emu_check_hit(Wg, X, pos, sp_apply(Sx, E.tile, E.dt));
+                    sp_emu_check_hit(Wg, X, HB + pos, E.dk, sp_apply(Sx, E.tile, E.dt));
 #endif
-                    cs = (int)pos;
+                    cs = (int)(HB + pos);
                     break;
                 }
                 pos = (pos + 1) & (SP_CAP - 1);
@@ -1084,28 +1153,31 @@ __device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, 
             if (cs < 0) X->overflow = 1;
             if (fresh) sp_new_state(Wg, X, (u32)cs, E.dk, sp_apply(Sx, E.tile, E.dt));  // next list index: slot, key and id
             const int pos_out = C->child_base[E.s] + (int)C->coff[E.it] + E.local;
-            const u32 ent = (cs < 0 ? SP_ENT_INVALID : (u32)cs) | ((u32)sp_discard_key(E.dt) << 14) | (E.rank == E.nk - 1 ? SP_ENT_LAST : 0u) |
-                            ((u32)E.count << 24);
+            const u32 ent = (cs < 0 ? SP_ENT_INVALID : (u32)cs) | ((u32)sp_discard_key(E.dt) << 15) | (E.rank == E.nk - 1 ? SP_ENT_LAST : 0u) |
+                            ((u32)E.count << 25);
             if (pos_out < SP_POOL) Wg->pool[pos_out] = ent;
             return cs;
         };
-        // The child cache (round 4): a child is looked up by ~6 parents, most of them neighbours in the level list, and five look-ups
-        // in six only need its slot.  A direct-mapped table in LDS remembers (state id -> slot) of the children this workgroup saw
-        // last: a hit costs one ds_read and no tag line from L2 / HBM (a 128-byte line per 8-byte tag otherwise).
-#if SP_CC_N > 0
-        unsigned long long* const cc = X->cc;
-        SP_ASSUME_LDS(cc);  // (a generic pointer would turn the look-up into a flat_load, which waits for every HBM gather in flight)
-#else
-        unsigned long long* const cc = nullptr;
-#endif
+        // A child is looked up by ~6 parents, most of them neighbours in the level list, and five look-ups in six only need its slot.
+        // mj_k_sp: the states that found a way in the LDS set (sp_set_find_or_claim: most rows whole, the first part of the heaviest)
+        // are found and placed there -- two ds_read_b128, one ds_cmpst per new state, no tag line from L2 / HBM (a 128-byte line per
+        // 8-byte tag), no L2 atomic, no second round trip; only a state whose four ways belong to others goes on to the HBM table.
+        // mj_k_sp_promo / mj_k_sp_wide (a parked row changes workgroups, LDS does not travel): a direct-mapped cache in LDS remembers
+        // (state id -> slot) of the children this workgroup saw last (round 4), the HBM table holds every state.
+        u64* const set = X->set;
+        SP_ASSUME_LDS(set);  // (a generic pointer would turn the look-up into a flat_load, which waits for every HBM gather in flight)
         const u64 cc_ep = (u64)X->cc_epoch << 42;
-        auto cc_look = [&](const Ent& E) -> int {
-            if (!cc || !E.on) return -1;
-            const u64 v = cc[E.pos & (SP_CC_N - 1)];
-            return (v >> 14) == (cc_ep | E.dk) ? (int)(v & 0x3FFFu) : -1;
+        auto look = [&](const Ent& E) -> int {
+            if (!E.on) return -1;
+            if constexpr (LDS_SET) {
+                return sp_set_find_or_claim(set, E.h, SP_TAG(E.dk, tag_ep), tag_ep);
+            } else {
+                const u64 v = set[sp_hash_pos(E.h) & (SP_SET_SLOTS - 1)];
+                return (v >> 14) == (cc_ep | E.dk) ? (int)(v & 0x3FFFu) : -1;
+            }
         };
         auto cc_put = [&](const Ent& E, int cs) {
-            if (cc && cs >= 0) cc[E.pos & (SP_CC_N - 1)] = ((cc_ep | E.dk) << 14) | (u64)(u32)cs;
+            if (!LDS_SET && cs >= 0) set[sp_hash_pos(E.h) & (SP_SET_SLOTS - 1)] = ((cc_ep | E.dk) << 14) | (u64)(u32)cs;
         };
         for (int e0 = 0; e0 < n_entries; e0 += 2 * SP_NT) {
             const bool two = e0 + SP_NT < n_entries;  // uniform: a round with at most 64 entries decodes one entry per lane (-0.9 %)
@@ -1114,15 +1186,16 @@ __device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, 
             B.on = false;
             if (two) B = decode(e0 + SP_NT + tid);
             u64 oa = 1ull, ob = 1ull;
-            const int ka = cc_look(A), kb = cc_look(B);
-            // five edges in six find their child already there: LOOK before claiming (a plain load; within a row a tag only ever goes
-            // from free -- zero or another row's epoch -- to its final value, so a stale value can only look free, which costs the
-            // atomic that would have been issued anyway).  mj_k_sp -3.0 % (round 4, same box): 144 M L2 atomics per launch
-            // become ~25 M.
-            if (A.on && ka < 0) oa = Wg->tag[A.pos];
-            if (B.on && kb < 0) ob = Wg->tag[B.pos];
-            if (A.on && ka < 0 && sp_tag_free(oa, tag_ep)) oa = sp_claim_tag(&Wg->tag[A.pos], SP_TAG(A.dk, tag_ep), oa);
-            if (B.on && kb < 0 && sp_tag_free(ob, tag_ep)) ob = sp_claim_tag(&Wg->tag[B.pos], SP_TAG(B.dk, tag_ep), ob);
+            const int ka = look(A), kb = look(B);
+            // the HBM table.  Five edges in six find their child already there: LOOK before claiming (a plain load; within a row a tag
+            // only ever goes from free -- zero or another row's epoch -- to its final value, so a stale value can only look free, which
+            // costs the atomic that would have been issued anyway).  mj_k_sp -3.0 % (round 4, same box): 144 M L2 atomics per launch
+            // became ~25 M.
+            const u32 pa = sp_hash_pos(A.h), pb = sp_hash_pos(B.h);
+            if (A.on && ka < 0) oa = Wg->tag[pa];
+            if (B.on && kb < 0) ob = Wg->tag[pb];
+            if (A.on && ka < 0 && sp_tag_free(oa, tag_ep)) oa = sp_claim_tag(&Wg->tag[pa], SP_TAG(A.dk, tag_ep), oa);
+            if (B.on && kb < 0 && sp_tag_free(ob, tag_ep)) ob = sp_claim_tag(&Wg->tag[pb], SP_TAG(B.dk, tag_ep), ob);
             if (A.on) {
                 const int cs = finish(A, oa, ka);
                 if (ka < 0) cc_put(A, cs);
@@ -1215,7 +1288,7 @@ __device__ SP_ATTR_EVAL0 void sp_eval_wave0(SpWork* W, SpCtx* X, float* WL, int 
     const int hp_own = hp_base + (int)assume_riichi + (int)(haitei && ln == T - 1), hp_last = hp_base + (int)haitei;
     const SP_HBM float* const nt_rows = (const SP_HBM float*)c_sp_nt + (size_t)__builtin_amdgcn_readfirstlane(min(X->n_left, SP_NT_ROWS - 1)) * (SP_NT_ROWS * SP_NT_STRIDE);
     const int last = max(end - 1, 0);
-    auto ld_slot = [&](int i) -> u32 { return sp_ld<u32>(elistB, 4u * (u32)min(i, last)); };  // hash slot | list index << 14
+    auto ld_slot = [&](int i) -> u32 { return sp_ld<u32>(elistB, 4u * (u32)min(i, last)); };  // slot | list index << 15
     SP_HBM SpF4* const scB = sp_uniform(&Wg->l0sc[0]);
     SP_HBM SpHdr* const hdrB = sp_uniform(&Wg->hdr[0]);
     auto ld_hdr = [&](u32 el) -> u64 { return sp_ld<unsigned long long>(hdrB, 16u * SP_EL_IDX(el)); };
@@ -1374,7 +1447,7 @@ __device__ SP_ATTR_EVAL void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
     SP_HBM u32* const elistB = sp_uniform(&Wg->elist[0]);
     SP_HBM u32* const poolB = sp_uniform(&Wg->pool[0]);
     SP_HBM SpHdr* const hdrB = sp_uniform(&Wg->hdr[0]);
-    auto ld_slot = [&](int i) -> u32 { return sp_ld<u32>(elistB, 4u * (u32)min(i, last)); };  // hash slot | list index << 14
+    auto ld_slot = [&](int i) -> u32 { return sp_ld<u32>(elistB, 4u * (u32)min(i, last)); };  // slot | list index << 15
     auto ld_hdr = [&](u32 el) -> u64 { return sp_ld<unsigned long long>(hdrB, 16u * SP_EL_IDX(el)); };
     auto ld_m = [&](u64 hdr) -> float { return sp_ld<float>(nt_rows, 4u * ((u32)min((int)((hdr >> 48) & 0xFF), SP_NT_ROWS - 1) * SP_NT_STRIDE + (u32)ln)); };
     auto ld_ent = [&](u32 at) -> u32 { return sp_ld<u32>(poolB, 4u * min(at, (u32)(SP_POOL - 1))); };
@@ -1534,7 +1607,7 @@ __device__ __forceinline__ void sp_sort_level(SpWork* W, int* hist /* LDS [64] *
     SP_HBM SpWork* const Wg = (SP_HBM SpWork*)W;
     const int tid = threadIdx.x;
     if (e - b <= SP_SORT_MIN) {  // a handful of states (the root level): one round of teams whatever the order
-        for (int i = b + tid; i < e; i += NT) Wg->elist[i] = Wg->list[i] | ((u32)i << 14);
+        for (int i = b + tid; i < e; i += NT) Wg->elist[i] = Wg->list[i] | ((u32)i << 15);
         __syncthreads();
         return;
     }
@@ -1550,7 +1623,7 @@ __device__ __forceinline__ void sp_sort_level(SpWork* W, int* hist /* LDS [64] *
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const int i = b + tid + q * NT;
-        my_slot[q] = i < e ? (Wg->list[i] | ((u32)i << 14)) : 0u;
+        my_slot[q] = i < e ? (Wg->list[i] | ((u32)i << 15)) : 0u;
         my_key[q] = i < e ? cost_key(i) : 0;
         if (i < e) atomicAdd(&hist[my_key[q]], 1);
     }
@@ -1566,7 +1639,7 @@ __device__ __forceinline__ void sp_sort_level(SpWork* W, int* hist /* LDS [64] *
         const int i = b + tid + q * NT;
         if (i < e) Wg->elist[b + atomicAdd(&hist[my_key[q]], 1)] = my_slot[q];
     }
-    for (int i = b + tid + 4 * NT; i < e; i += NT) Wg->elist[b + atomicAdd(&hist[cost_key(i)], 1)] = Wg->list[i] | ((u32)i << 14);
+    for (int i = b + tid + 4 * NT; i < e; i += NT) Wg->elist[b + atomicAdd(&hist[cost_key(i)], 1)] = Wg->list[i] | ((u32)i << 15);
     __syncthreads();
 }
 
@@ -2128,11 +2201,12 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
     __shared__ unsigned long long s_stat[SP_ERR_STATS];  // this workgroup's share of SpParams::err, flushed once (see sp_light_row)
     if (threadIdx.x < SP_ERR_STATS) s_stat[threadIdx.x] = 0ull;
     __shared__ typename SpLds<NT>::Teams s_tm;
-#if SP_CC_N > 0
-    __shared__ unsigned long long s_cc[SP_CC_N];  // the child cache of the expansion (sp_expand_chunk)
-    for (int i = threadIdx.x; i < SP_CC_N; i += NT) s_cc[i] = 0ull;
-    unsigned n_graph_rows = 0;
-#endif
+    // the expansion's table in LDS (sp_expand_chunk).  A parked row is finished by another workgroup and LDS does not travel, so only
+    // mj_k_sp, which neither parks rows nor takes them over, keeps states there; the other two kernels keep the child cache.
+    constexpr bool LDS_SET = !WIDE && !PROMO;
+    __shared__ __attribute__((aligned(16))) u64 s_set[SP_SET_SLOTS];
+    for (int i = threadIdx.x; i < SP_SET_SLOTS; i += NT) s_set[i] = 0ull;
+    unsigned n_graph_rows = 0;  // (child cache)
     // mj_k_sp: workgroup b owns work area b (and moves to spare area grid + k after its k-th promotion); mj_k_sp_wide: the promoted row's area
     SpWork* W = WIDE ? P.work + P.n_narrow + P.promo_cap + blockIdx.x : P.work + blockIdx.x;
     SpWork* const W_own = W;
@@ -2263,20 +2337,18 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         }
         bool parked = false;
         if (with_probs) {
-#if SP_CC_N > 0
-            // a new row = a new epoch of the child cache (8 bits, 1..255; when they have gone round the cache is wiped)
-            n_graph_rows++;
-            if ((n_graph_rows & 255u) == 0u) {
+            if constexpr (!LDS_SET) {
+                // a new row = a new epoch of the child cache (8 bits, 1..255; when they have gone round the cache is wiped)
                 n_graph_rows++;
-                for (int i = tid; i < SP_CC_N; i += NT) s_cc[i] = 0ull;
+                if ((n_graph_rows & 255u) == 0u) {
+                    n_graph_rows++;
+                    for (int i = tid; i < SP_SET_SLOTS; i += NT) s_set[i] = 0ull;
+                }
             }
             if (tid == 0) {
-                X.cc = s_cc;
+                X.set = s_set;
                 X.cc_epoch = n_graph_rows & 255u;
             }
-#else
-            if (tid == 0) X.cc = nullptr;
-#endif
             if (promoted) {
                 if (tid == 0) {
                     X.prof = P.prof;
@@ -2287,6 +2359,8 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                 // a new row = a new epoch of the hash tags
                 if (tag_epoch >= SP_EPOCH_WRAP) {  // wrapped (once in 2 M rows): wipe the table, start over
                     for (int i = tid; i < SP_CAP; i += NT) W->tag[i] = 0ull;
+                    if constexpr (LDS_SET)  // (the set's ways carry the same epoch)
+                        for (int i = tid; i < SP_SET_SLOTS; i += NT) s_set[i] = 0ull;
                     tag_epoch = 0;
                     __syncthreads();
                 }
@@ -2298,7 +2372,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                     const int c = tid;
                     SpState s = root;
                     if (can_discard) sp_discard(s, X.cand_tile[c]);
-                    X.cand_slot[c] = sp_insert(W, &X, sp_dk_add(0ull, -1, can_discard ? X.cand_tile[c] : -1), s, -1, -1);
+                    X.cand_slot[c] = sp_insert<LDS_SET>(W, &X, sp_dk_add(0ull, -1, can_discard ? X.cand_tile[c] : -1), s, -1, -1);
                 }
                 __syncthreads();
                 if (tid == 0) {
@@ -2350,7 +2424,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                 // the same for 4 states as for 16, so idle wavefronts are the only thing to lose)
                 const int ns = min(SP_NS, max(1, (e - b + NT / SP_NT - 1) / (NT / SP_NT)));
                 for (int c0 = b + ns * (tid / SP_NT); c0 < e; c0 += ns * (NT / SP_NT))
-                    sp_expand_chunk(W, &X, &s_tm.wchunk[tid / SP_NT], c0, min(ns, e - c0), lv);
+                    sp_expand_chunk<LDS_SET>(W, &X, &s_tm.wchunk[tid / SP_NT], c0, min(ns, e - c0), lv);
                 __syncthreads();
                 if (tid == 0) {
                     X.lvl_begin[lv - 1] = e;
