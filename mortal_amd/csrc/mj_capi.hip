@@ -1082,6 +1082,10 @@ int mj_counters(MjPool* P, uint64_t out[8], void* stream) {
 #ifdef MJ_EMU
 // emulator builds only (not part of the C-ABI): states placed in mj_k_sp's LDS set / in the HBM table since the library was loaded
 void mj_emu_sp_placed(uint64_t out[2]) { out[0] = g_sp_emu_placed[0]; out[1] = g_sp_emu_placed[1]; }
+// claims lost since then: LDS set to the same id / to another id, HBM table to the same id / to another id (mj_sp.hip: g_sp_emu_lost)
+void mj_emu_sp_lost_claims(uint64_t out[4]) {
+    for (int k = 0; k < 2; k++) out[k] = g_sp_emu_lost[2 + k], out[2 + k] = g_sp_emu_lost[k] - g_sp_emu_lost[2 + k];
+}
 #endif
 
 int mj_sp_phase_ticks(MjPool* P, uint64_t out[8], void* stream) {

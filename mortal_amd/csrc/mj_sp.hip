@@ -27,6 +27,9 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#ifdef MJ_EMU
+#include <algorithm>  // (sp_emu_check_unique)
+#endif
 
 #include "mj_rules.h"
 #include "mj_sptab.h"
@@ -463,10 +466,18 @@ template <typename Tp> __device__ __forceinline__ Tp* sp_opaque_s(Tp* p) { asm v
 #define SP_ATTR_EVAL0 __noinline__
 #endif
 
+#ifdef MJ_EMU
+// claims lost since the library was loaded (only an emulator whose atomics yield can lose one), to the same id / to another id:
+// [0..1] every claim (sp_claim_tag), [2..3] those of them on a way of the LDS set (sp_set_find_or_claim); the rest is the HBM table
+inline unsigned long long g_sp_emu_lost[4];
+#endif
 template <class TagP>
 MJD u64 sp_claim_tag(TagP tagp, u64 h, u64 seen) {  // claim a slot seen empty (holding `seen`): atomicCAS(tag, seen, h) (relaxed, agent scope)
     u64 expected = seen;                            // -> 0 = claimed, else the tag found there (of this row: only this workgroup writes its table)
     __hip_atomic_compare_exchange_strong(tagp, &expected, h, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef MJ_EMU
+    if (expected != seen) g_sp_emu_lost[expected != h ? 1 : 0]++;
+#endif
     return expected == seen ? 0ull : expected;
 }
 // hash-set insert of the state `base` + draw `tile` - discard `dt` (either may be -1) with id `dk`: returns the slot or -1 on
@@ -502,8 +513,21 @@ inline void sp_emu_check_hit(WP W, SpCtx* X, u32 slot, u64 dk, const SpState& st
     sp_key(st, k);
     const u32 idx = W->idx_of[slot];
     if (idx >= (u32)SP_CAP) return;
+    // An index of an EARLIER row is stale too, and may well name the same id (ids are relative to the row's roots, and an id hashes to
+    // the same ways in every row): its record is that row's.  Seen once atomics yield (the claimer waits in sp_new_state's atomicAdd while
+    // another lane hits its way).  Indices below n_list hold records of this row, written whole.
+    if (idx >= (u32)X->n_list) return;
     const auto& e = W->keys[idx];
     if (e.dk == dk && (e.k0 != k[0] || e.k1 != k[1] || e.k2 != k[2] || e.k3 != k[3])) X->overflow = 1;
+}
+// A race that placed one id in two slots would change no value of the row (both nodes evaluate alike), only its number of states:
+// at the end of a row's expansion the ids of keys[0 .. n_list) must be pairwise distinct, or the row counts as overflowed.
+template <class WP>
+inline void sp_emu_check_unique(WP W, SpCtx* X) {
+    std::vector<u64> ids((size_t)min(X->n_list, SP_CAP));
+    for (size_t i = 0; i < ids.size(); i++) ids[i] = W->keys[i].dk;
+    std::sort(ids.begin(), ids.end());
+    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) X->overflow = 1;
 }
 inline unsigned long long g_sp_emu_placed[2];  // states placed in the LDS set / in the HBM table (tests: a small set must send states both ways)
 #endif
@@ -527,6 +551,9 @@ __device__ __forceinline__ int sp_set_find_or_claim(u64* set, u32 h, u64 tag, u3
         if (!sp_tag_free(w[i], ep)) continue;  // another state of this row: for good
         const u32 slot = 2 * b[i >> 1] + (i & 1);
         const u64 old = sp_claim_tag(&set[slot], tag, w[i]);
+#ifdef MJ_EMU
+        if (old != 0ull) g_sp_emu_lost[2 + (old != tag ? 1 : 0)]++;
+#endif
         if (old == 0ull) return (int)slot | (1 << 16);
         if (old == tag) return (int)slot;  // another lane has just placed this very state here
     }
@@ -2433,6 +2460,9 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                 __syncthreads();
             }
             t_2 = wall_clock64();
+#ifdef MJ_EMU
+            if (tid == 0 && !parked) sp_emu_check_unique(W, &X);  // (its verdict is read after the row's last barrier)
+#endif
             // evaluate bottom-up
             if (!parked)
             for (int lv = 0; lv <= cur_shanten; lv++) {

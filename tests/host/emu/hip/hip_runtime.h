@@ -11,6 +11,17 @@
 // a collective reached by only part of its group is reported as a deadlock instead of returning stale lanes.
 // `__shared__` variables become function-local statics (one workgroup runs at a time); atomics are plain read-modify-writes
 // (fibers are never pre-empted).  No timing model, no memory model: it finds logic errors, not races between wavefronts.
+//
+// -DEMU_ATOMIC_YIELD (through EMU_EXTRA_FLAGS, tests/host/build_emu.py) is an opt-in mode in which a look-then-claim can be LOST, as on
+// the hardware: every atomic (atomicAdd/Or/And/Min/Max/CAS/Exch, emu_cas, the __hip_atomic_* forms) yields to the scheduler BEFORE it
+// acts, so all lanes of a pass take their snapshot of memory, then all of them issue their compare-and-swap, then one wins -- the SIMT
+// order of a wavefront.  The scheduler visits the fibers of a pass in an order permuted by a seeded generator (environment variable
+// EMU_SCHED_SEED, default 0), so the winner of a race changes with the seed, from pass to pass and across wavefronts.  A lane that
+// sits in an atomic's yield is neither finished nor blocked: a collective reached by the other lanes of its group keeps waiting for
+// it (arrivals are counted against the lanes still alive), every pass visits every fiber once whatever the order, so the lane is
+// resumed and arrives, and the yield itself counts as progress -- the deadlock report fires only when every live lane is blocked in a
+// barrier, as without the flag.  Still no memory model (every store is visible at once) and no timing.  Without the flag none of this
+// is compiled.
 #pragma once
 #define MJ_EMU 1
 
@@ -117,6 +128,10 @@ struct State {
     std::vector<GroupBar> gbar;           // [n_waves][width 1..64][group]
     std::vector<unsigned long long> xbuf;  // [n_waves][width][2][64]
     std::vector<char> dyn_shared;
+#ifdef EMU_ATOMIC_YIELD
+    std::vector<int> order;  // the fibers in the order a scheduler pass visits them
+    unsigned long long rng = 0;
+#endif
 };
 inline State& S() {
     static State s;
@@ -147,6 +162,22 @@ inline void wait_for_gen(const unsigned* gen, unsigned val) {
     }
     f.wait_gen = nullptr;
 }
+#ifdef EMU_ATOMIC_YIELD
+// the pre-emption point in front of an atomic (kernel code only: the host side of the library has no scheduler to yield to)
+inline void atomic_yield() {
+    State& s = S();
+    if (!s.body) return;
+    s.progress++;  // runnable, not blocked: a pass that only brought lanes to their atomics is no deadlock
+    to_scheduler(s.fibers[s.cur]);
+}
+inline unsigned long long sched_rand() {  // splitmix64
+    State& s = S();
+    unsigned long long z = (s.rng += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+#endif
 inline void release_block_barrier_if_complete() {
     State& s = S();
     if (s.bar_arrived > 0 && s.bar_arrived >= s.alive) {
@@ -253,6 +284,14 @@ inline void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void
     s.gbar.assign((size_t)n_waves * 65 * WAVE, GroupBar());
     s.xbuf.assign((size_t)n_waves * 65 * 2 * WAVE, 0ull);
     if (s.dyn_shared.size() < shmem + 64) s.dyn_shared.resize(shmem + 64);
+#ifdef EMU_ATOMIC_YIELD
+    if (s.order.empty()) {  // first launch of the process
+        const char* seed = getenv("EMU_SCHED_SEED");
+        s.rng = 0x5851F42D4C957F2Dull ^ (seed ? strtoull(seed, nullptr, 0) : 0ull);
+    }
+    s.order.resize(n);
+    for (int t = 0; t < n; t++) s.order[t] = t;
+#endif
     for (unsigned bz = 0; bz < grid.z; bz++)
         for (unsigned by = 0; by < grid.y; by++)
             for (unsigned bx = 0; bx < grid.x; bx++) {
@@ -280,7 +319,13 @@ inline void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void
                 }
                 while (s.alive > 0) {
                     const unsigned long long before = s.progress;
+#ifdef EMU_ATOMIC_YIELD
+                    for (int i = n - 1; i > 0; i--) std::swap(s.order[i], s.order[(int)(sched_rand() % (unsigned)(i + 1))]);
+                    for (int k = 0; k < n; k++) {
+                        const int t = s.order[k];
+#else
                     for (int t = 0; t < n; t++) {
+#endif
                         if (s.fibers[t].done) continue;
                         if (s.fibers[t].wait_gen && *s.fibers[t].wait_gen == s.fibers[t].wait_val) continue;  // still blocked
                         s.cur = t;
@@ -377,6 +422,28 @@ inline long long wall_clock64() { return (long long)(emu::now_ms() * 1e5); }
 using std::max;
 using std::min;
 
+#ifdef EMU_ATOMIC_YIELD
+// ---- atomics that can be lost: each yields before it acts (see the top of the file)
+#define EMU_Y emu::atomic_yield()
+template <class T, class U> inline T atomicAdd(T* p, U v) { EMU_Y; T o = *p; *p = (T)(o + (T)v); return o; }
+template <class T, class U> inline T atomicOr(T* p, U v) { EMU_Y; T o = *p; *p = (T)(o | (T)v); return o; }
+template <class T, class U> inline T atomicAnd(T* p, U v) { EMU_Y; T o = *p; *p = (T)(o & (T)v); return o; }
+template <class T, class U> inline T atomicMin(T* p, U v) { EMU_Y; T o = *p; if ((T)v < o) *p = (T)v; return o; }
+template <class T, class U> inline T atomicMax(T* p, U v) { EMU_Y; T o = *p; if ((T)v > o) *p = (T)v; return o; }
+template <class T, class U, class V> inline T atomicCAS(T* p, U cmp, V val) { EMU_Y; T o = *p; if (o == (T)cmp) *p = (T)val; return o; }
+template <class T, class U> inline T atomicExch(T* p, U v) { EMU_Y; T o = *p; *p = (T)v; return o; }
+template <class P, class T> inline bool emu_cas(P p, T* expected, T desired) {
+    EMU_Y;
+    if (*p == *expected) { *p = desired; return true; }
+    *expected = *p;
+    return false;
+}
+#define __hip_atomic_compare_exchange_strong(p, expected, desired, so, fo, scope) emu_cas((p), (expected), (desired))
+#define __hip_atomic_fetch_or(p, v, order, scope) atomicOr((p), (v))
+#define __hip_atomic_fetch_add(p, v, order, scope) atomicAdd((p), (v))
+#define __hip_atomic_load(p, order, scope) (EMU_Y, *(p))
+#define __hip_atomic_store(p, v, order, scope) (EMU_Y, *(p) = (v))
+#else
 // ---- atomics (fibers are never pre-empted)
 template <class T, class U> inline T atomicAdd(T* p, U v) { T o = *p; *p = (T)(o + (T)v); return o; }
 template <class T, class U> inline T atomicOr(T* p, U v) { T o = *p; *p = (T)(o | (T)v); return o; }
@@ -395,6 +462,7 @@ template <class P, class T> inline bool emu_cas(P p, T* expected, T desired) {
 #define __hip_atomic_fetch_add(p, v, order, scope) atomicAdd((p), (v))
 #define __hip_atomic_load(p, order, scope) (*(p))
 #define __hip_atomic_store(p, v, order, scope) (*(p) = (v))
+#endif
 
 // ---- runtime API (host memory stands in for HBM)
 inline hipError_t hipMalloc(void** p, size_t n) {
