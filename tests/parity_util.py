@@ -100,6 +100,16 @@ def fake_q_values(masks, rows, cycle, seed):
     return np.ascontiguousarray(q, dtype=np.float32)
 
 
+def census_of(stats):
+    """tests/situation_census.py over the device logs of a `run_lockstep(compare_logs=True)` run, as a sorted dict."""
+    import situation_census
+
+    total = situation_census.Counter()
+    for log in stats["device_logs"]:
+        total.update(situation_census.census(log))
+    return dict(sorted(total.items()))
+
+
 def run_lockstep(oracle, n_tables, version, max_cycles=4000, seeds=None, compare_obs=True, obs_every=1,
                  policy_seed=0x9E3779B97F4A7C15, quick_eval=True, sp_rows_checked=False, verbose=True,
                  policy="random", guard=False, oracle_obs=False, compare_logs=False, deal_algo=0, refill=0, min_games=2,
@@ -112,6 +122,10 @@ def run_lockstep(oracle, n_tables, version, max_cycles=4000, seeds=None, compare
     at cycle ((t * 2654435761 mod 2^32) >> 8) % S through the refill path (mj_pool_set_start_stagger, mj_step.hip: mj_k_park /
     mj_k_refill), i.e. on (nonce + stride, key) as game id t + n_tables; the oracle slot idles until that cycle the same way.
     obs_cycles: explicit set of cycles whose obs are compared (overrides obs_every); threads: oracle encode threads;
+    policy: "random", "greedy", "tsumogiri", or a callable (arena, masks, rows, cycle) -> actions that reads the oracle side only.
+    A run that `max_cycles` stops before a table has finished (the steering policies under which nobody wins) compares that table's
+    event logs as prefixes of equal length: both sides have polled the same number of times, so neither log may be longer than the
+    other by more than the events of one poll, and every event both hold must agree; a finished table's logs are equal in full.
     obs_slice: compare the obs in slices of that many rows (the oracle encodes slice by slice: the 65,536-table pool's 8 GB
     batch never exists twice on the host); obs_slice_max = k > 0: only k of those slices, spread evenly over the batch (rows are
     ordered by table, and a table's phase does not depend on its index: any slice holds the batch's mix of decisions)."""
@@ -276,7 +290,9 @@ def run_lockstep(oracle, n_tables, version, max_cycles=4000, seeds=None, compare
                     lines.append(f"  plane {q}: oracle {inv_o[r, q].tolist()}\n            gpu    {inv_g[r, q].tolist()}")
                 raise AssertionError("\n".join(lines))
             stats["oracle_obs_checked"] = stats.get("oracle_obs_checked", 0) + n
-        if policy == "greedy":
+        if callable(policy):  # tests/steering.py: (arena, masks, rows, cycle) -> actions, from the oracle side alone
+            act = np.ascontiguousarray(policy(arena, masks_o, rows_o, cycle), dtype=np.int32)
+        elif policy == "greedy":
             d0 = DISCARD_ROW[version]
             act = greedy_actions(masks_o, rows_o, cycle, obs_g[:, d0:d0 + 3].cpu().numpy(), policy_seed)
             if n:  # the device-side port of the same policy (mj_k_greedy_policy, the benchmark's realistic-hand workload)
@@ -344,19 +360,26 @@ def run_lockstep(oracle, n_tables, version, max_cycles=4000, seeds=None, compare
         from mortal_amd import mjai_log
 
         n_ev = 0
+        device_logs = []
         for g, words in enumerate(pool.read_logs()):
             got = mjai_log.decode_events(words)
             want = arena.log(g)
             dump = lambda e: json.dumps(e, separators=(",", ":"))
+            if not both[g]:  # stopped in mid-game: prefixes of equal length (see the docstring)
+                assert abs(len(got) - len(want)) <= 8 and min(len(got), len(want)) > 0, (g, len(got), len(want))
+                k = min(len(got), len(want))
+                got, want = got[:k], want[:k]
             if [dump(e) for e in got] != [dump(e) for e in want]:
                 k = 0
                 while k < min(len(got), len(want)) and dump(got[k]) == dump(want[k]):
                     k += 1
                 raise AssertionError(f"game {g}: event {k} of {len(want)} differs:\n oracle {want[k] if k < len(want) else None}\n"
                                      f" gpu    {got[k] if k < len(got) else None}")
+            device_logs.append(got)
             n_ev += len(got)
         stats["log_events_checked"] = n_ev
+        stats["device_logs"] = device_logs  # decoded from the device's own words (tests/situation_census.py reads them)
     if verbose:
-        print("lockstep", stats)
+        print("lockstep", {k: v for k, v in stats.items() if k != "device_logs"})
     pool.close()
     return stats

@@ -105,8 +105,9 @@ def test_lockstep_quick_eval_disabled(oracle):
 def test_lockstep_greedy_policy_v3(oracle):
     """A shanten-greedy policy (always agari, mostly riichi, calls) drives the games through tenpai / riichi / ron /
     furiten / kan paths that uniform-random play rarely reaches; v3 obs compared every cycle."""
-    st = parity_util.run_lockstep(oracle, 256, version=3, max_cycles=3000, obs_every=1, policy="greedy")
+    st = parity_util.run_lockstep(oracle, 256, version=3, max_cycles=3000, obs_every=1, policy="greedy", compare_logs=True)
     assert st["scores_checked"] == 256
+    print("situation census, greedy 256 tables:", parity_util.census_of(st))  # (the logs are kept for it: what this policy reaches)
 
 
 def test_lockstep_greedy_policy_v4_sp(oracle):
@@ -143,9 +144,11 @@ def test_lockstep_event_logs(oracle):
     st = parity_util.run_lockstep(oracle, 128, version=3, max_cycles=4000, compare_obs=False, policy="greedy",
                                   compare_logs=True)
     assert st["scores_checked"] == 128 and st["log_events_checked"] > 100000
+    print("situation census, greedy 128 tables:", parity_util.census_of(st))
     st = parity_util.run_lockstep(oracle, 64, version=3, max_cycles=4000, compare_obs=False, policy="random",
                                   compare_logs=True, seeds=parity_util.default_seeds(64, 777))
     assert st["scores_checked"] == 64
+    print("situation census, random 64 tables:", parity_util.census_of(st))
 
 
 def test_lockstep_tsumogiri_reference_seeds(oracle):
