@@ -20,6 +20,7 @@
  *   mj_greedy_policy      (no reference counterpart: tenpai-seeking benchmark / test policy)
  *   mj_results            arena/result.rs:19-30 GameResult.scores; arena/one_vs_three.rs:55-60 ranking input
  *   mj_counters           arena/game.rs:298-311 cycles/actions progress counters
+ *   mj_pool_stat, mj_stat_logs   stat.rs:263-441 Stat::from_game, summed as stat.rs:443-498 Stat::from_dir sums the games of a run
  */
 #ifndef MORTAL_AMD_H
 #define MORTAL_AMD_H
@@ -168,6 +169,35 @@ int mj_greedy_policy(MjPool* pool, int agent, const uint8_t* masks_dev, const fl
 int mj_counters(MjPool* pool, uint64_t out[8], void* stream);
 /* Final scores [n_games_total][4] and done flags (0 running, 1 finished, 2 aborted on error) to host memory. */
 int mj_results(MjPool* pool, int32_t* scores_out, uint8_t* done_out, void* stream);
+/* ---- libriichi's Stat (stat.rs:30-126) reduced from packed event logs on the device (kernel: mortal_amd/csrc/mj_stat.hip).
+ * One int64 counter per field, in the declaration order of stat.rs:30-126 (= mortal_amd/stat.py STAT_FIELDS): */
+#define MJ_STAT_FIELDS 44
+enum MjStatField {
+    MJ_ST_GAME = 0, MJ_ST_ROUND, MJ_ST_OYA, MJ_ST_POINT, MJ_ST_RANK_1, MJ_ST_RANK_2, MJ_ST_RANK_3, MJ_ST_RANK_4, MJ_ST_TOBI,
+    MJ_ST_FUURO, MJ_ST_FUURO_NUM, MJ_ST_FUURO_POINT, MJ_ST_FUURO_AGARI, MJ_ST_FUURO_AGARI_JUN, MJ_ST_FUURO_AGARI_POINT,
+    MJ_ST_FUURO_HOUJUU, MJ_ST_AGARI, MJ_ST_AGARI_AS_OYA, MJ_ST_AGARI_JUN, MJ_ST_AGARI_POINT_OYA, MJ_ST_AGARI_POINT_KO,
+    MJ_ST_HOUJUU, MJ_ST_HOUJUU_JUN, MJ_ST_HOUJUU_TO_OYA, MJ_ST_HOUJUU_POINT_TO_OYA, MJ_ST_HOUJUU_POINT_TO_KO,
+    MJ_ST_RIICHI, MJ_ST_RIICHI_AS_OYA, MJ_ST_RIICHI_JUN, MJ_ST_RIICHI_AGARI, MJ_ST_RIICHI_AGARI_POINT, MJ_ST_RIICHI_AGARI_JUN,
+    MJ_ST_RIICHI_HOUJUU, MJ_ST_RIICHI_RYUKYOKU, MJ_ST_RIICHI_POINT, MJ_ST_CHASING_RIICHI, MJ_ST_RIICHI_GOT_CHASED,
+    MJ_ST_DAMA_AGARI, MJ_ST_DAMA_AGARI_JUN, MJ_ST_DAMA_AGARI_POINT, MJ_ST_RYUKYOKU, MJ_ST_RYUKYOKU_POINT, MJ_ST_YAKUMAN,
+    MJ_ST_NAGASHI_MANGAN
+};
+/* stat.rs:263-441 Stat::from_game over n_logs packed event logs (LG_* words, the words mj_log_read returns or mortal_amd/mjai_log.py
+ * encode_events builds; host arrays; no pool needed, only a device).  Log i = words[off[i] .. off[i + 1]); seats[i] bit s = seat s of
+ * log i is counted; groups[i] bit s = which of the two totals that seat goes to.  per_seat rows of seats that are not counted are 0.
+ * counts_out = {logs reduced, logs skipped (length 0), malformed logs (the event chain runs past the end of the log or meets an
+ * event type outside 1..14; they contribute nothing)}.  A log that stops between two events, in the middle of a kyoku or of a
+ * hanchan, is reduced like the reference reduces that prefix.  Synchronous. */
+int mj_stat_logs(const uint64_t* words_host, const uint32_t* off_host /* [n_logs + 1] */, int n_logs,
+                 const uint8_t* seats_host /* [n_logs] 4-bit masks, NULL = all */, const uint8_t* groups_host /* NULL = 0 */,
+                 int64_t* totals_out /* [2][MJ_STAT_FIELDS] */, int64_t* per_seat_out /* NULL or [n_logs][4][MJ_STAT_FIELDS] */,
+                 int64_t counts_out[3], void* stream);
+/* The same over the pool's own device log, in place: every table whose game has finished (done == 1); running tables and
+ * tables in error are skipped and counted.  group bit = agent_of_seat.  Needs mj_pool_enable_log; ordered behind the steps already
+ * launched on `stream`; synchronous.  An error in refill mode: a restarted table's log has been rewound. */
+int mj_pool_stat(MjPool* pool, const uint8_t* seats_host /* [n_tables], NULL = all */, int64_t* totals_out,
+                 int64_t* per_seat_out /* NULL or [n_tables][4][MJ_STAT_FIELDS] */, int64_t counts_out[3], void* stream);
+
 /* First table in error: returns its error code (>0) and index, or 0. */
 int mj_pool_first_error(MjPool* pool, int* table_out, void* stream);
 

@@ -82,7 +82,7 @@ class BatchRunner:
 
     pool_cls = TablePool  # the test suite substitutes the host emulation of the same kernels (tests/host/emu_pool.py)
 
-    def __init__(self, engines, seeds, agent_of_seat, device=None, deal_algo=None, keep_log=False):
+    def __init__(self, engines, seeds, agent_of_seat, device=None, deal_algo=None, keep_log=False, keep_stat=False):
         self.engines = engines
         self.cfg = [_check_engine(e) for e in engines]
         dev = device
@@ -98,7 +98,9 @@ class BatchRunner:
         self.pool = self.pool_cls(n, version=self.cfg[0]["version"], deal_algo=deal_algo, device=str(self.device))
         self.device = self.pool.device
         self.any_mjai_log = any(c["mjai_log"] for c in self.cfg)
-        if keep_log or self.any_mjai_log:  # mjai-log engines read the kyoku's events from the device log
+        # mjai-log engines read the kyoku's events from the device log; keep_stat needs the log on the device and nothing else
+        # (no q-values, no per-decision metadata: those are keep_log's)
+        if keep_log or keep_stat or self.any_mjai_log:
             self.pool.enable_log()
         self.seeds = list(seeds)
         self.agent_of_seat = np.asarray(agent_of_seat, dtype=np.uint8)
@@ -331,6 +333,19 @@ class BatchRunner:
                                 eng.end_game(idx, [int(x) for x in scores[g]])
         return scores
 
+    def agent_stats(self):
+        """After run(): [Stat of agent 0's seats, Stat of agent 1's seats] over every game, reduced on the device from the
+        event log (keep_stat / keep_log)."""
+        totals, _rows, counts = self.pool.log_stat()
+        if counts["reduced"] != self.pool.n_tables:
+            raise MortalAmdError(f"stats: {counts['skipped']} games unfinished or in error, {counts['malformed']} malformed logs")
+        return totals
+
+    def stats(self):
+        """After run(): {engine name: Stat}, what `Stat.from_dir(log_dir, name)` gives on the dumped logs (engines of the same
+        name are summed there too, stat.rs:443-498)."""
+        return _stats_by_name([c["name"] for c in self.cfg], [t.counters() for t in self.agent_stats()])
+
     @staticmethod
     def _meta(batch, row, tag, with_batch=False):
         """Metadata of one decision (agent/mortal.rs:161-186 gen_meta + :575-591), keys in the order of mjai::Metadata."""
@@ -378,6 +393,24 @@ class BatchRunner:
         self.pool.close()
 
 
+def _stats_by_name(names, agent_counters):
+    """Per-agent counters -> {engine name: Stat}; a single engine plays both agents' seats."""
+    from .stat import Stat
+
+    names = list(names) * 2 if len(names) == 1 else list(names)
+    out = {}
+    for name, c in zip(names, agent_counters):
+        out[name] = out.get(name, Stat()) + Stat.from_counters(c)
+    return out
+
+
+def _reduce_device(backend, dev):
+    """Where a collective's tensor lives: the pool's GPU under nccl (the current one for a rank without games), else the host."""
+    if backend != "nccl":
+        return torch.device("cpu")
+    return dev if dev is not None else torch.device(f"cuda:{torch.cuda.current_device()}")
+
+
 def _rank_by_player(scores):
     """rankings.rs:8-21: stable sort by -score; ties favour the lower seat."""
     order = sorted(range(4), key=lambda i: -int(scores[i]))
@@ -390,10 +423,14 @@ def _rank_by_player(scores):
 class OneVsThree:
     """libriichi.arena.OneVsThree (arena/one_vs_three.rs:17-113)."""
 
-    def __init__(self, *, disable_progress_bar=False, log_dir=None, deal_algo=None):
+    def __init__(self, *, disable_progress_bar=False, log_dir=None, deal_algo=None, collect_stat=False):
         self.disable_progress_bar = disable_progress_bar
         self.log_dir = log_dir
         self.deal_algo = deal_algo  # None = pool.default_deal_algo() (rand 0.9.1 unless MORTAL_AMD_DEAL_ALGO says otherwise)
+        # our extension: py_vs_py leaves {engine name: Stat} of the whole run in self.stats, counted on the device -- what
+        # Stat.from_dir(log_dir, name) computes from the dumped files (mortal/player.py:62-71), without writing or reading them
+        self.collect_stat = collect_stat
+        self.stats = None
 
     def py_vs_py(self, challenger, champion, seed_start, seed_count):
         """Returns the rank histogram [1st, 2nd, 3rd, 4th] of the challenger over seed_count*4 hanchan."""
@@ -411,11 +448,15 @@ class OneVsThree:
         aos = np.array([0xF & ~(1 << (g % 4)) for g in range(g0, g1)], dtype=np.uint8)
         rankings = [0, 0, 0, 0]
         dev = None
+        counters = [[0] * 44, [0] * 44]  # Stat counters of the challenger's / the champion's seats (collect_stat)
         if g1 > g0:
-            runner = BatchRunner([challenger, champion], seeds, aos, keep_log=self.log_dir is not None, deal_algo=self.deal_algo)
+            runner = BatchRunner([challenger, champion], seeds, aos, keep_log=self.log_dir is not None, deal_algo=self.deal_algo,
+                                 keep_stat=self.collect_stat)
             dev = runner.device
             try:
                 scores = runner.run(progress=None if self.disable_progress_bar else f"rank {rank}" if world > 1 else "")
+                if self.collect_stat:
+                    counters = [t.counters() for t in runner.agent_stats()]
                 if self.log_dir is not None:
                     runner.dump_logs(self.log_dir, 4)
             finally:
@@ -423,9 +464,13 @@ class OneVsThree:
             for i, g in enumerate(range(g0, g1)):
                 rankings[_rank_by_player(scores[i])[g % 4]] += 1  # one_vs_three.rs:55-60
         if world > 1:
-            red_dev = dev if (backend == "nccl" and dev is not None) else torch.device(
-                f"cuda:{torch.cuda.current_device()}") if backend == "nccl" else torch.device("cpu")
+            red_dev = _reduce_device(backend, dev)
             rankings = sharding.allreduce_rank_histogram(rankings, device=red_dev)
+            if self.collect_stat:
+                flat = sharding.allreduce_counters(counters[0] + counters[1], device=red_dev)
+                counters = [flat[:44], flat[44:]]
+        if self.collect_stat:
+            self.stats = _stats_by_name([_check_engine(e)["name"] for e in (challenger, champion)], counters)
         return rankings
 
     def ako_vs_py(self, engine, seed_start, seed_count):
@@ -438,28 +483,43 @@ class OneVsThree:
 class TwoVsTwo:
     """libriichi.arena.TwoVsTwo (arena/two_vs_two.rs:17-110): seed_count*2 hanchan, returns None."""
 
-    def __init__(self, *, disable_progress_bar=False, log_dir=None, deal_algo=None):
+    def __init__(self, *, disable_progress_bar=False, log_dir=None, deal_algo=None, collect_stat=False):
         self.disable_progress_bar = disable_progress_bar
         self.log_dir = log_dir
         self.deal_algo = deal_algo  # None = pool.default_deal_algo() (rand 0.9.1 unless MORTAL_AMD_DEAL_ALGO says otherwise)
+        # our extension: py_vs_py leaves {engine name: Stat} of the whole run in self.stats, counted on the device -- what
+        # Stat.from_dir(log_dir, name) computes from the dumped files (mortal/player.py:62-71), without writing or reading them
+        self.collect_stat = collect_stat
+        self.stats = None
 
     def py_vs_py(self, challenger, champion, seed_start, seed_count):
         from . import sharding
 
         n = int(seed_count) * 2
-        rank, world, _backend = sharding.dist_info()  # one process per GPU: contiguous seed ranges, nothing to reduce
+        rank, world, backend = sharding.dist_info()  # one process per GPU: contiguous seed ranges; only collect_stat reduces
         g0, g1 = sharding.shard_range(n, rank, world, group=2) if world > 1 else (0, n)
         seeds = [(int(seed_start[0]) + g // 2, int(seed_start[1])) for g in range(g0, g1)]  # two_vs_two.rs:138-140
         # split A: challenger at seats 0,2; split B: 1,3 (two_vs_two.rs:142-172)
         aos = np.array([0b1010 if g % 2 == 0 else 0b0101 for g in range(g0, g1)], dtype=np.uint8)
+        counters = [[0] * 44, [0] * 44]
+        dev = None
         if g1 > g0:
-            runner = BatchRunner([challenger, champion], seeds, aos, keep_log=self.log_dir is not None, deal_algo=self.deal_algo)
+            runner = BatchRunner([challenger, champion], seeds, aos, keep_log=self.log_dir is not None, deal_algo=self.deal_algo,
+                                 keep_stat=self.collect_stat)
+            dev = runner.device
             try:
                 self.last_scores = runner.run(progress=None if self.disable_progress_bar else "")
+                if self.collect_stat:
+                    counters = [t.counters() for t in runner.agent_stats()]
                 if self.log_dir is not None:
                     runner.dump_logs(self.log_dir, 2)
             finally:
                 runner.close()
+        if self.collect_stat:
+            if world > 1:
+                flat = sharding.allreduce_counters(counters[0] + counters[1], device=_reduce_device(backend, dev))
+                counters = [flat[:44], flat[44:]]
+            self.stats = _stats_by_name([_check_engine(e)["name"] for e in (challenger, champion)], counters)
         return None
 
     def ako_vs_py(self, *a, **k):

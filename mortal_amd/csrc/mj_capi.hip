@@ -1,5 +1,5 @@
 // C-ABI host side (include/mortal_amd.h): pool life-cycle and kernel launches.  One translation unit for the whole
-// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip.
+// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip.
 // Host float math below builds bit-exact LUTs: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,7 @@
 #include "mj_replay.hip"
 #include "mj_encode.hip"
 #include "mj_sp.hip"
+#include "mj_stat.hip"
 
 static_assert(sizeof(MjAlgoQuery) == 72, "MjAlgoQuery layout");
 // include/mortal_amd.h mj_algo_query: one thread per query, the same device functions the step / encode / SP kernels call
@@ -1131,6 +1132,90 @@ int mj_results(MjPool* P, int32_t* scores, uint8_t* done, void* stream) {
     HIP_OK(hipMemcpy(scores, P->final_scores, (size_t)P->n_games_total * 4 * sizeof(int), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(done, P->final_done, (size_t)P->n_games_total, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---------------------------------------------------------------- Stat over event logs (stat.rs:263-441; mj_stat.hip)
+namespace {
+struct StatBuf {  // device memory of one mj_stat_logs / mj_pool_stat call, freed on every return path
+    void* p = nullptr;
+    ~StatBuf() { if (p) hipFree(p); }
+    int from_host(const void* src, size_t bytes, hipStream_t s) {
+        HIP_OK(hipMalloc(&p, std::max(bytes, (size_t)8)));
+        if (bytes) HIP_OK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
+        return 0;
+    }
+};
+// launches mj_k_log_stat with K's inputs, copies the outputs to the host and waits for them
+int stat_run(StatParams K, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
+             hipStream_t s) {
+    if (!totals_out || !counts_out) return fail("null totals / counts buffer");
+    const size_t n = (size_t)K.n_logs, n_out = 2 * MJ_STAT_FIELDS + 3;
+    StatBuf b_seats, b_out, b_per;
+    if (seats_host) {
+        if (b_seats.from_host(seats_host, n, s)) return -1;
+        K.seats = (const uint8_t*)b_seats.p;
+    }
+    HIP_OK(hipMalloc(&b_out.p, n_out * sizeof(int64_t)));
+    HIP_OK(hipMemsetAsync(b_out.p, 0, n_out * sizeof(int64_t), s));
+    K.totals = (unsigned long long*)b_out.p;
+    K.counts = K.totals + 2 * MJ_STAT_FIELDS;
+    if (per_seat_out) {
+        HIP_OK(hipMalloc(&b_per.p, n * 4 * MJ_STAT_FIELDS * sizeof(int64_t)));
+        K.per_seat = (long long*)b_per.p;
+    }
+    const int grid = (int)std::min<size_t>((n + STAT_WAVES - 1) / STAT_WAVES, STAT_GRID_MAX);
+    hipLaunchKernelGGL(mj_k_log_stat, dim3(grid), dim3(STAT_THREADS), 0, s, K);
+    HIP_OK(hipGetLastError());
+    int64_t out[2 * MJ_STAT_FIELDS + 3];
+    HIP_OK(hipMemcpyAsync(out, b_out.p, sizeof out, hipMemcpyDeviceToHost, s));
+    if (per_seat_out)
+        HIP_OK(hipMemcpyAsync(per_seat_out, b_per.p, n * 4 * MJ_STAT_FIELDS * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    memcpy(totals_out, out, 2 * MJ_STAT_FIELDS * sizeof(int64_t));
+    memcpy(counts_out, out + 2 * MJ_STAT_FIELDS, 3 * sizeof(int64_t));
+    return 0;
+}
+}  // namespace
+
+int mj_stat_logs(const uint64_t* words_host, const uint32_t* off_host, int n_logs, const uint8_t* seats_host,
+                 const uint8_t* groups_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3], void* stream) {
+    if (!totals_out || !counts_out) return fail("null totals / counts buffer");
+    memset(totals_out, 0, 2 * MJ_STAT_FIELDS * sizeof(int64_t));
+    memset(counts_out, 0, 3 * sizeof(int64_t));
+    if (n_logs <= 0) return n_logs < 0 ? fail("mj_stat_logs: negative n_logs") : 0;
+    if (!off_host) return fail("mj_stat_logs: null offsets");
+    for (int i = 0; i < n_logs; i++)  // the kernel trusts the offsets: a log lies inside [0, off[n_logs])
+        if (off_host[i] > off_host[i + 1]) return fail("mj_stat_logs: offsets of log " + std::to_string(i) + " decrease");
+    const size_t n_words = off_host[n_logs];
+    if (n_words && !words_host) return fail("mj_stat_logs: null words");
+    hipStream_t s = (hipStream_t)stream;
+    StatBuf b_words, b_off, b_groups;
+    if (b_words.from_host(words_host, n_words * sizeof(uint64_t), s) || b_off.from_host(off_host, ((size_t)n_logs + 1) * sizeof(uint32_t), s)) return -1;
+    StatParams K{};
+    K.words = (const uint64_t*)b_words.p;
+    K.off = (const uint32_t*)b_off.p;
+    K.n_logs = n_logs;
+    if (groups_host) {
+        if (b_groups.from_host(groups_host, (size_t)n_logs, s)) return -1;
+        K.groups = (const uint8_t*)b_groups.p;
+    }
+    return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, s);
+}
+
+int mj_pool_stat(MjPool* P, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
+                 void* stream) {
+    if (!P) return fail("null pool");
+    if (!P->log) return fail("mj_pool_stat: the event log is not enabled (mj_pool_enable_log)");
+    if (P->refill_stride) return fail("mj_pool_stat: not available in refill mode (a restarted table's log has been rewound)");
+    hipStream_t s = (hipStream_t)stream;
+    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap, 0));  // behind the last step, whatever its stream
+    StatParams K{};
+    K.words = P->log;
+    K.len = P->log_len;
+    K.stride = P->log_cap;
+    K.blocks = P->blocks;
+    K.n_logs = P->n_tables;
+    return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, s);
 }
 
 __global__ void mj_k_first_error(const TableBlock* blocks, int n_tables, unsigned long long* out) {

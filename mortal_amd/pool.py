@@ -118,6 +118,19 @@ class TablePool:
             out += [buf[i, :lens[t0 + i]].copy() for i in range(k)]
         return out
 
+    def log_stat(self, seats=None, per_seat=False):
+        """libriichi's Stat of every finished game, reduced from the device log in place (mj_pool_stat; needs enable_log).
+        seats: 4-bit mask per table (None = all).  -> (totals [Stat of agent 0's seats, Stat of agent 1's seats], per-seat
+        int64 array [n_tables, 4, 44] or None, counts dict(reduced, skipped, malformed)), as stat.stat_logs; tables still
+        playing or in error are skipped."""
+        from .stat import _stat_call
+
+        def call(p_seats, p_totals, p_rows, p_counts):
+            if self._L.mj_pool_stat(self.h, p_seats, p_totals, p_rows, p_counts, self._stream()) < 0:
+                raise MortalAmdError(self._L.mj_last_error().decode())
+
+        return _stat_call(call, self.n_tables, seats, per_seat)
+
     # ---- log replay (dataset loader)
     def replay_load(self, scripts, tracked, always_include_kan_select=True, nonces=None, keys=None):
         """scripts: one uint64 word array per table (mjai_log.encode_events); tracked: 4-bit seat mask per table;

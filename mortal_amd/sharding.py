@@ -54,3 +54,11 @@ def allreduce_rank_histogram(local_hist, group=None, device=None):
     t = torch.as_tensor(list(local_hist), dtype=torch.int64, device=device or torch.device("cpu"))
     dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     return [int(x) for x in t.tolist()]
+
+
+def allreduce_counters(local_counters, group=None, device=None):
+    """Sum over the ranks of a flat sequence of int64 counters (the Stat counters of `collect_stat`: Stat::from_dir sums the
+    games of a whole run, stat.rs:443-498)."""
+    t = torch.as_tensor([int(x) for x in local_counters], dtype=torch.int64, device=device or torch.device("cpu"))
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return [int(x) for x in t.tolist()]

@@ -3,6 +3,9 @@
 A pure event-stream reduction (stat.rs:263-441 `from_game`): no game-state replay is needed, so this lives on the host.
 Counter names, update rules, derived-rate getters and the text report follow the reference one to one
 (fields stat.rs:30-126, getters :500-779, Display :128-256).
+
+`stat_logs` (and `TablePool.log_stat`, `BatchRunner.stats`) compute the same 44 counters on the device, from the packed event
+words instead of JSON files (mortal_amd/csrc/mj_stat.hip); `Stat.from_game` is the reading they are tested against.
 """
 import glob
 import gzip
@@ -19,6 +22,7 @@ _FIELDS = [
     "riichi_ryukyoku", "riichi_point", "chasing_riichi", "riichi_got_chased",
     "dama_agari", "dama_agari_jun", "dama_agari_point", "ryukyoku", "ryukyoku_point", "yakuman", "nagashi_mangan",
 ]
+STAT_FIELDS = tuple(_FIELDS)  # the counters' order in every device result (include/mortal_amd.h MjStatField)
 
 
 def _div(a, b):
@@ -50,6 +54,17 @@ class Stat:
 
     def __eq__(self, other):
         return isinstance(other, Stat) and all(getattr(self, f) == getattr(other, f) for f in _FIELDS)
+
+    # ---- the counters as a flat sequence in STAT_FIELDS order (the device's form of a Stat)
+    @staticmethod
+    def from_counters(seq):
+        seq = [int(x) for x in seq]
+        if len(seq) != len(_FIELDS):
+            raise ValueError(f"expected {len(_FIELDS)} counters, got {len(seq)}")
+        return Stat(**dict(zip(_FIELDS, seq)))
+
+    def counters(self):
+        return [getattr(self, f) for f in _FIELDS]
 
     # ---- stat.rs:263-441
     @staticmethod
@@ -285,3 +300,62 @@ class Stat:
 
     def __repr__(self):
         return "Stat { " + ", ".join(f"{f}: {getattr(self, f)}" for f in _FIELDS) + " }"
+
+
+def _stat_call(call, n_logs, seats, per_seat):
+    """Shared by stat_logs and TablePool.log_stat: allocate the outputs, run `call(seats ptr, totals ptr, per-seat ptr, counts
+    ptr)`, wrap the result."""
+    import numpy as np
+
+    if seats is not None:
+        seats = np.ascontiguousarray(seats, dtype=np.uint8)
+        if seats.shape != (n_logs,):
+            raise ValueError(f"seats: expected {n_logs} masks, got shape {seats.shape}")
+    totals = np.zeros((2, len(_FIELDS)), dtype=np.int64)
+    rows = np.zeros((n_logs, 4, len(_FIELDS)), dtype=np.int64) if per_seat else None
+    counts = np.zeros(3, dtype=np.int64)
+    call(seats.ctypes.data if seats is not None else None, totals.ctypes.data, rows.ctypes.data if per_seat else None,
+         counts.ctypes.data)
+    return ([Stat.from_counters(totals[0]), Stat.from_counters(totals[1])], rows,
+            dict(reduced=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2])))
+
+
+def stat_logs(words_list, seats=None, groups=None, per_seat=False, lib=None):
+    """`Stat.from_game` of every (log, seat) on the device, from packed event words (mjai_log.encode_events, TablePool.read_logs).
+
+    words_list: one uint64 array per game; seats: 4-bit mask per game of the seats to count (None = all four); groups: per
+    game, bit s = which of the two totals seat s is added to (None = the first).  Returns (totals [Stat, Stat], per-seat int64
+    array [n, 4, 44] in STAT_FIELDS order or None, counts dict(reduced, skipped, malformed)): an empty log is skipped, a
+    malformed one (its event chain runs past its end, or an unknown event type) is counted and contributes nothing.
+    `lib` is for the test suite (the host emulation of the same sources)."""
+    import ctypes
+
+    import numpy as np
+
+    n = len(words_list)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in words_list])
+    if int(off[-1]) >= 1 << 32:
+        raise ValueError("stat_logs: more than 2^32 words in one call")
+    off = off.astype(np.uint32)
+    words = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64) for x in words_list]) if n else np.zeros(0),
+                                 dtype=np.uint64)
+    if groups is not None:
+        groups = np.ascontiguousarray(groups, dtype=np.uint8)
+        if groups.shape != (n,):
+            raise ValueError(f"groups: expected {n} bytes, got shape {groups.shape}")
+    stream = None
+    if lib is None:
+        import torch
+
+        from ._lib import lib
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call(p_seats, p_totals, p_rows, p_counts):
+        rc = lib.mj_stat_logs(words.ctypes.data, off.ctypes.data, n, p_seats, groups.ctypes.data if groups is not None else None,
+                              p_totals, p_rows, p_counts, stream)
+        if rc < 0:
+            from ._lib import MortalAmdError
+            raise MortalAmdError(lib.mj_last_error().decode())
+
+    return _stat_call(call, n, seats, per_seat)
