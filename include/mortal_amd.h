@@ -71,7 +71,14 @@ int mj_pool_set_refill(MjPool* pool, uint64_t nonce_stride);
 int mj_pool_set_start_stagger(MjPool* pool, uint32_t cycles, void* stream);
 
 /* One arena cycle.  actions_dev[a] = int32 device array with one action id (0..45) per row of agent a's previous
- * batch (NULL on the first cycle or when that agent had no rows). */
+ * batch (NULL on the first cycle or when that agent had no rows).
+ * An id whose mask bit was clear puts that table -- and no other -- in error MJ_ERR_ILLEGAL_ACTION (1): it leaves play in this
+ * step with done flag 2 (mj_results), is counted by counters [1] (games) and [2] (errors) and reported by mj_pool_first_error.
+ * That includes every id outside 0..45, and 45 (pass) on a row whose seat cannot pass (an own-turn row: mask[45] clear).  This
+ * is stricter than the reference, whose decoder ends in `_ => Event::None` (agent/mortal.rs:571-572): there a masked policy never
+ * produces such an id and what follows one is an accident (the board takes "nobody reacted" and draws again for a seat that
+ * never discarded), here a garbage answer -- a NaN q row under the agari guard selects 45 -- must end in a code, not in a game
+ * that silently diverges. */
 int mj_step(MjPool* pool, const int32_t* actions_dev0, const int32_t* actions_dev1, void* stream);
 /* Same, with the q-values of each batch (f32 device array [n_rows][46], agent/mortal.rs:126,150).  Needed when an agent
  * was configured with enable_rule_based_agari_guard: an agari (action 43) that PlayerState::rule_based_agari
@@ -117,7 +124,9 @@ int mj_table_query(MjPool* pool, int table, int seat, int what, const int32_t* a
 /* Number of policy rows per agent produced by the last mj_step.  Waits for the row counts of THAT step (recorded on the stream the
  * step was launched on; `stream` is only used before any step has run) -- it does NOT drain the stream: the snapshot kernel queued
  * behind the counts may still be running when the call returns.  mj_encode / mj_encode_oracle order themselves behind it: on the
- * step's stream by stream order, on any other stream by waiting for the snapshot's event. */
+ * step's stream by stream order, on any other stream by waiting for the snapshot's event.
+ * Fails with "row capacity exceeded" when a batch has more rows than the pool's max_rows: n_rows_out is still filled in, the batch
+ * stays invalid and mj_encode / mj_encode_oracle / mj_replay_meta refuse it until the next successful mj_rows_count. */
 int mj_rows_count(MjPool* pool, int32_t n_rows_out[2], void* stream);
 /* Device array of row descriptors of agent a: table | seat << 28 | is_kan_select << 31. */
 const uint32_t* mj_rows_dev(MjPool* pool, int agent);

@@ -745,12 +745,14 @@ int mj_rows_count(MjPool* P, int32_t out[2], void* stream) {
     if (!P) return fail("null pool");
     if (P->ev_rows) HIP_OK(hipEventSynchronize(P->ev_rows));  // (the counts' copy; the snapshot queued behind it may still be running)
     else HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    P->last_rows[0] = P->n_rows_host[0];
-    P->last_rows[1] = P->n_rows_host[1];
-    P->rows_valid = true;
-    out[0] = P->last_rows[0];
-    out[1] = P->last_rows[1];
+    out[0] = P->n_rows_host[0];
+    out[1] = P->n_rows_host[1];
+    // a batch that does not fit rows[] stays invalid (rows_valid false, last_rows never above max_rows): mj_encode, mj_encode_oracle
+    // and mj_replay_meta refuse it with their "mj_rows_count must be called" error instead of walking rows[] past its allocation
     if (out[0] > P->max_rows || out[1] > P->max_rows) return fail("row capacity exceeded");
+    P->last_rows[0] = out[0];
+    P->last_rows[1] = out[1];
+    P->rows_valid = true;
     return 0;
 }
 const uint32_t* mj_rows_dev(MjPool* P, int agent) { return P ? P->rows[agent & 1] : nullptr; }

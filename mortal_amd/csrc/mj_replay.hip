@@ -246,8 +246,12 @@ __global__ __launch_bounds__(64) void mj_k_replay(ReplayParams P) {
             if (nr) break;
         }
         P.cursor[table] = cur;
-        if (cur >= n_words && !(F(flags) & TF_DONE)) {
+        // a table in error stops where its log stopped being a legal game and leaves play like a finished one, counted in games and
+        // in errors as mj_k_step counts it: a caller that waits for `games` to reach the number of logs terminates
+        const bool failed = F(err) != MJ_OK;
+        if ((cur >= n_words || failed) && !(F(flags) & TF_DONE)) {
             F(flags) |= TF_DONE;
+            if (failed) atomicAdd(&P.counters[2], 1ull);
             atomicAdd(&P.counters[1], 1ull);
         }
     }

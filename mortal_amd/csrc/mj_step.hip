@@ -265,7 +265,11 @@ template <class LN> MJDN Reaction decode_action(const LN& L, int s, int action, 
             if (!(cans & CAN_RYUKYOKU)) { set_err(L, MJ_ERR_ILLEGAL_ACTION); return r; }
             r.type = RX_RYUKYOKU;
             return r;
-        default: return r;  // 45 = pass
+        default:
+            // 45 = pass, where the seat may pass (the complement of mask[45], mj_encode.hip); 45 on an own-turn row and every id
+            // outside 0..45 is an error -- stricter than the reference's `_ => Event::None` (mortal.rs:571-572), see mortal_amd.h
+            if (action != 45 || !(cans & CAN_PASS)) set_err(L, MJ_ERR_ILLEGAL_ACTION);
+            return r;
     }
 }
 
