@@ -475,12 +475,23 @@ MJD bool agari_better(Agari a, Agari b) {  // a > b per agari.rs:180-195
 // a run is closed right before the next one opens and once at the end — the same bit positions.
 struct Tile14 {
     u64 lo, hi;
-    MJD int at(u32 i) const { return (int)(((i < 8 ? lo : hi) >> (8 * (i & 7))) & 0xFF); }
+    // REGS: both words by value, then a select.  `i < 8 ? lo : hi` selects an ADDRESS, which pins the struct in scratch memory (one
+    // indexed scratch load per use); the out-of-line agari functions keep that form -- their register allocation, and through the
+    // clobber sets of the calls that of the kernels around them, was tuned with it.  The SP scoring loop takes the register form.
+    template <bool REGS> MJD int at(u32 i) const {
+        if constexpr (REGS) {
+            const u64 l = lo, h = hi;
+            return (int)(((i < 8 ? l : h) >> (8 * (i & 7))) & 0xFF);
+        } else {
+            return (int)(((i < 8 ? lo : hi) >> (8 * (i & 7))) & 0xFF);
+        }
+    }
 };
 MJD u32 tile14_and_key(Hand h, Tile14& t14) {
     t14.lo = t14.hi = 0;
     u32 key = 0, n14 = 0;
     int bit = -1, prev = -2;
+#pragma unroll 1
     for (u64 m = h.nonzero_mask(); m; m &= m - 1) {
         const int t = __ffsll((long long)m) - 1, c = h.get(t);
         const bool same_run = t < 27 && t == prev + 1 && (t % 9) != 0;
@@ -520,17 +531,18 @@ struct DivWork {
     bool has_chitoi, has_chuuren, has_ittsuu, has_ryanpeikou, has_ipeikou;
     bool wt_minkou;  // winning_tile_makes_minkou
 };
+template <bool REGS>
 MJD DivWork div_init(const AgariIn& in, const Tile14& t14, u32 v) {  // agari.rs:126-157, 288-338
     DivWork w;
-    w.pair_tile = t14.at((v >> 6) & 15);
+    w.pair_tile = t14.template at<REGS>((v >> 6) & 15);
     const int nk = v & 7, ns = (v >> 3) & 7;
     w.n_mk = nk;
     w.n_ms = ns;
     w.kotsu = w.shuntsu = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        if (i < nk) melds_put(w.kotsu, i, t14.at((v >> (10 + i * 4)) & 15));
-        if (i < ns) melds_put(w.shuntsu, i, t14.at((v >> (10 + (nk + i) * 4)) & 15));
+        if (i < nk) melds_put(w.kotsu, i, t14.template at<REGS>((v >> (10 + i * 4)) & 15));
+        if (i < ns) melds_put(w.shuntsu, i, t14.template at<REGS>((v >> (10 + (nk + i) * 4)) & 15));
     }
     int k = nk;
 #pragma unroll
@@ -747,7 +759,10 @@ MJD Agari div_search_yakus(const AgariIn& in, const DivWork& w, u64 hand_nz, boo
 }
 
 // agari.rs:260-288.  any_only => has_yaku()
-MJDN Agari agari_search(const MjTablesDev& T, const AgariIn& in, bool any_only) {
+// The body is an inline core: agari_search below is its out-of-line form (the step kernel, mj_algo_query), while the SP kernel's level-0
+// scoring loop inlines it, so that an item's AgariIn lives in registers instead of travelling through a stack frame by reference.
+template <bool REGS>
+MJD Agari agari_search_inl(const MjTablesDev& T, const AgariIn& in, bool any_only) {
     Agari best = {0, 0, 0};
     if (in.is_menzen && calc_kokushi(in.tehai) == -1) {
         best.kind = 2;
@@ -761,8 +776,9 @@ MJDN Agari agari_search(const MjTablesDev& T, const AgariIn& in, bool any_only) 
     const u32* rec = T.agari_divs + (size_t)idx * 5;
     const int n = (int)rec[0];
     const u64 hand_nz = in.tehai.nonzero_mask();
+#pragma unroll 1
     for (int i = 0; i < n; i++) {
-        const DivWork w = div_init(in, t14, rec[1 + i]);
+        const DivWork w = div_init<REGS>(in, t14, rec[1 + i]);
         const Agari a = div_search_yakus(in, w, hand_nz, any_only);
         if (a.kind == 0) continue;
         if (any_only) return a;
@@ -770,9 +786,13 @@ MJDN Agari agari_search(const MjTablesDev& T, const AgariIn& in, bool any_only) 
     }
     return best;
 }
-// agari.rs:228-258
-MJDN Agari agari_full(const MjTablesDev& T, const AgariIn& in, int additional_hans, int doras) {
-    Agari a = agari_search(T, in, false);
+MJDN Agari agari_search(const MjTablesDev& T, const AgariIn& in, bool any_only) { return agari_search_inl<false>(T, in, any_only); }
+// agari.rs:228-258.  INLINE_SEARCH: the search is part of the caller's code (SP scoring loop) / a call of agari_search (everyone else).
+template <bool INLINE_SEARCH>
+MJD Agari agari_full_inl(const MjTablesDev& T, const AgariIn& in, int additional_hans, int doras) {
+    Agari a;
+    if constexpr (INLINE_SEARCH) a = agari_search_inl<true>(T, in, false);
+    else a = agari_search(T, in, false);
     if (a.kind == 1) { a.han += additional_hans + doras; return a; }
     if (a.kind == 2) return a;
     Agari none = {0, 0, 0};
@@ -784,10 +804,14 @@ MJDN Agari agari_full(const MjTablesDev& T, const AgariIn& in, int additional_ha
     if (idx < 0) return none;
     const u32* rec = T.agari_divs + (size_t)idx * 5;
     int fu = -1;
-    for (int i = 0; i < (int)rec[0]; i++) fu = max(fu, div_calc_fu(in, div_init(in, t14, rec[1 + i]), false));
+#pragma unroll 1
+    for (int i = 0; i < (int)rec[0]; i++) fu = max(fu, div_calc_fu(in, div_init<INLINE_SEARCH>(in, t14, rec[1 + i]), false));
     if (fu < 0) return none;
     Agari r = {1, fu, additional_hans + doras};
     return r;
+}
+MJDN Agari agari_full(const MjTablesDev& T, const AgariIn& in, int additional_hans, int doras) {
+    return agari_full_inl<false>(T, in, additional_hans, doras);
 }
 MJD Point agari_point(Agari a, bool is_oya) { return a.kind == 2 ? point_yakuman(is_oya, a.han) : point_calc(is_oya, a.fu, a.han); }
 

@@ -429,6 +429,10 @@ MJD bool sp_tag_free(u64 t, u32 ep) { return (u32)((t >> 42) & SP_EPOCH_MAX) != 
 //  * a __noinline__ callee saves and restores its callee-saved VGPRs on every call: 37 stores + 37 loads per expansion chunk =
 //    19 KB per 16 states.  The expansion is therefore inlined into the kernel (one call site); the evaluation / level-0 functions
 //    stay calls (a call there is a wavefront's whole share of a level; inlining them was measured slower: their loops then spill).
+//    Those calls are cheap -- 1 saved VGPR for the probe, 12-20 for an evaluation instantiation, 14 for the scoring pass, once per
+//    wavefront and level, under 100 registers per wavefront and row.  The per-ITEM traffic once blamed on them sat inside the level-0
+//    scoring loop: an AgariIn built on the stack (~50 B a lane), a call of agari_full through a pointer to it, the callee's reloads,
+//    register saves and scratch-indexed tile list.  That loop now makes no call and has no frame (sp_l0_score_all, sp_get_score).
 //  * lane-derived constants (lane -> suit / state index, LDS addresses) are loop-invariant, so the compiler computed them at the
 //    top of the kernel and spilled them (50 stores up front, reloads inside the probe passes).  An opaque copy of the lane id per
 //    row / per chunk stops the hoisting: the constants are recomputed (1-2 VALU) where they are used.
@@ -611,28 +615,64 @@ MJD SpState sp_state_of(const NodeT& n) {
     return s;
 }
 
-// get_score (calc.rs:640-758).  `s` already contains the winning tile.
-__device__ bool sp_get_score(const MjTablesDev& T, const SpCtx* X, const SpState& s, int win_tile, float scores[4]) {
+// A wave-uniform value out of LDS into a scalar register (every lane of the wavefront is active where this is used).
+MJD int sp_uniform(int v) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MJ_EMU)
+    return __builtin_amdgcn_readfirstlane(v);
+#else
+    return v;
+#endif
+}
+// The part of get_score's input that is the same for every work item of a row: read from SpCtx once per scoring call
+// (sp_l0_score_all), kept in scalar registers across its item loop.  Only the hand and the winning tile change per item.
+struct SpScoreRow {
+    u32 chis, pons, minkans, ankans;
+    int n_chis, n_pons, n_minkans, n_ankans;
+    int is_menzen, prefer_riichi, bakaze, jikaze, n_dora, num_doras_in_fuuro;
+    int dora0, dora1, dora2, dora3, dora4;  // the dora tiles (next of each indicator); scalars: static indices only
+};
+MJD SpScoreRow sp_score_row(const SpCtx* X) {
+    SP_ASSUME_LDS(X);
+    SpScoreRow R;
+    const Melds& xm = X->melds;  // member-wise (a struct copy is a memcpy, which keeps the generic address space of X: flat loads)
+    R.chis = (u32)sp_uniform((int)xm.chis); R.pons = (u32)sp_uniform((int)xm.pons);
+    R.minkans = (u32)sp_uniform((int)xm.minkans); R.ankans = (u32)sp_uniform((int)xm.ankans);
+    R.n_chis = sp_uniform(xm.n_chis); R.n_pons = sp_uniform(xm.n_pons);
+    R.n_minkans = sp_uniform(xm.n_minkans); R.n_ankans = sp_uniform(xm.n_ankans);
+    R.is_menzen = sp_uniform(X->is_menzen); R.prefer_riichi = sp_uniform(X->prefer_riichi);
+    R.bakaze = sp_uniform(X->bakaze); R.jikaze = sp_uniform(X->jikaze);
+    R.n_dora = sp_uniform(X->n_dora); R.num_doras_in_fuuro = sp_uniform(X->num_doras_in_fuuro);
+    R.dora0 = sp_uniform(tile_next(X->dora_ind[0])); R.dora1 = sp_uniform(tile_next(X->dora_ind[1]));
+    R.dora2 = sp_uniform(tile_next(X->dora_ind[2])); R.dora3 = sp_uniform(tile_next(X->dora_ind[3]));
+    R.dora4 = sp_uniform(tile_next(X->dora_ind[4]));
+    return R;
+}
+
+// get_score (calc.rs:640-758).  `s` already contains the winning tile.  Everything is inlined into the scoring loop: the AgariIn
+// below never has an address, so the decomposition, yaku and fu of an item run on registers (agari_full_inl; the out-of-line
+// agari_full took it by reference: ~50 B of stores per item, a call, and the callee's reloads and register saves).
+__device__ __forceinline__ bool sp_get_score(const SpScoreRow& R, const SpState& s, int win_tile, float scores[4]) {
+    const MjTablesDev& T = c_mj_tables;  // named directly: constant address space (a reference parameter would be a flat pointer)
     AgariIn in;
     in.tehai = s.h;
-    {   // member-wise (a struct copy is a memcpy, which keeps the generic address space of X: flat loads, both wait counters; with one
-        // kernel the compiler knew X's LDS address, with three kernels sharing this function it does not)
-        const Melds& xm = X->melds;
-        in.m.chis = xm.chis; in.m.pons = xm.pons; in.m.minkans = xm.minkans; in.m.ankans = xm.ankans;
-        in.m.n_chis = xm.n_chis; in.m.n_pons = xm.n_pons; in.m.n_minkans = xm.n_minkans; in.m.n_ankans = xm.n_ankans;
-    }
-    in.is_menzen = X->is_menzen != 0;
-    in.bakaze = X->bakaze;
-    in.jikaze = X->jikaze;
+    in.m.chis = R.chis; in.m.pons = R.pons; in.m.minkans = R.minkans; in.m.ankans = R.ankans;
+    in.m.n_chis = (u8)R.n_chis; in.m.n_pons = (u8)R.n_pons; in.m.n_minkans = (u8)R.n_minkans; in.m.n_ankans = (u8)R.n_ankans;
+    in.is_menzen = R.is_menzen != 0;
+    in.bakaze = R.bakaze;
+    in.jikaze = R.jikaze;
     in.winning_tile = deaka(win_tile);
     in.is_ron = false;
-    const bool is_oya = X->jikaze == T_E;
-    const int additional = X->is_menzen ? (X->prefer_riichi ? 2 : 1) : 0;
+    const bool is_oya = R.jikaze == T_E;
+    const int additional = R.is_menzen ? (R.prefer_riichi ? 2 : 1) : 0;
     int num_doras = 0;
-    for (int i = 0; i < X->n_dora; i++) num_doras += s.h.get(tile_next(X->dora_ind[i]));
-    num_doras += __popc(s.akas & 7) + X->num_doras_in_fuuro;
+    if (0 < R.n_dora) num_doras += s.h.get(R.dora0);
+    if (1 < R.n_dora) num_doras += s.h.get(R.dora1);
+    if (2 < R.n_dora) num_doras += s.h.get(R.dora2);
+    if (3 < R.n_dora) num_doras += s.h.get(R.dora3);
+    if (4 < R.n_dora) num_doras += s.h.get(R.dora4);
+    num_doras += __popc(s.akas & 7) + R.num_doras_in_fuuro;
     num_doras &= 0xFF;
-    Agari a = agari_full(T, in, additional, num_doras);
+    Agari a = agari_full_inl<true>(T, in, additional, num_doras);
     if (a.kind == 0) return false;
     if (a.kind == 2) {
         float v = (float)tsumo_total(point_yakuman(is_oya, a.han), is_oya);
@@ -640,8 +680,8 @@ __device__ bool sp_get_score(const MjTablesDev& T, const SpCtx* X, const SpState
         return true;
     }
     const int fu = a.fu, han = a.han & 0xFF;
-    const bool assume_riichi = X->is_menzen && X->prefer_riichi;
-    if (assume_riichi && X->n_dora == 1) {
+    const bool assume_riichi = R.is_menzen && R.prefer_riichi;
+    if (assume_riichi && R.n_dora == 1) {
         // indicator tiles left in the wall per number of copies in the hand (scalars: a dynamically indexed local array
         // would live in scratch), over the hand's tile kinds only
         int n1 = 0, n2 = 0, n3 = 0, n4 = 0;
@@ -674,11 +714,11 @@ __device__ bool sp_get_score(const MjTablesDev& T, const SpCtx* X, const SpState
             }
             scores[i] = sc;
         }
-    } else if (assume_riichi && X->n_dora > 1) {
+    } else if (assume_riichi && R.n_dora > 1) {
         float pt[16];
 #pragma unroll
         for (int k = 0; k < 16; k++) pt[k] = (float)tsumo_total(point_calc(is_oya, fu, (han + k) & 0xFF), is_oya);
-        const float* ur = SP_URADORA[X->n_dora - 1];
+        const float* ur = SP_URADORA[R.n_dora - 1];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             float sc = 0.f;
@@ -702,25 +742,25 @@ __device__ bool sp_get_score(const MjTablesDev& T, const SpCtx* X, const SpState
 //   probe : sp_l0_probe_chunk — which draws win (34 shanten probes per state) -> draw entries, one work item per entry
 //   score : THREAD per item, dense across the workgroup                  -> 4 scores per work item (SpWork::l0sc)
 //   sum   : team per state — sp_eval_wave0 accumulates the scores in the reference's order
-__device__ __forceinline__ void sp_l0_score(const MjTablesDev& Tb, SpWork* W, const SpCtx* X, u32 item, int item_idx) {
-    SP_ASSUME_LDS(X);
+__device__ __forceinline__ void sp_l0_score(SpWork* W, const SpScoreRow& R, u32 item, int item_idx) {
     const int li = item & 0x3FFF, t = (item >> 19) & 63, variant = (item >> 25) & 1;  // list index of the state, winning tile
     SP_HBM SpWork* const Wg = (SP_HBM SpWork*)W;
     SpState S1 = sp_state_of(Wg->keys[li]);
     const int tile = variant ? akaize(t) : t;
     sp_deal(S1, tile);
     float scv[4];
-    const bool yaku = sp_get_score(Tb, X, S1, tile, scv);  // a hand with a yaku scores > 0: all-zero scores mark "no yaku" for the summation
+    const bool yaku = sp_get_score(R, S1, tile, scv);  // a hand with a yaku scores > 0: all-zero scores mark "no yaku" for the summation
     SP_HBM SpF4& dst = Wg->l0sc[item_idx];
     dst.x = yaku ? scv[0] : 0.f; dst.y = yaku ? scv[1] : 0.f; dst.z = yaku ? scv[2] : 0.f; dst.w = yaku ? scv[3] : 0.f;
 }
 
 // The dense scoring pass of one wavefront: its share of the row's work items in ONE call (a call per item and lane saved and restored the
-// function's 18 callee-saved VGPRs every 64 items).
-__device__ SP_ATTR_L0S void sp_l0_score_all(const MjTablesDev& Tb, SpWork* W, const SpCtx* X, int n_items, int tid, int stride) {
-    SP_ASSUME_LDS(X);
+// function's 18 callee-saved VGPRs every 64 items).  The item loop itself makes no call and touches no stack: the row's constants are
+// read once, an item's hand goes to the inlined agari code in registers (tests/test_sp_score_isa.py pins both).
+__device__ SP_ATTR_L0S void sp_l0_score_all(SpWork* W, const SpCtx* X, int n_items, int tid, int stride) {
+    const SpScoreRow R = sp_score_row(X);
     const SP_HBM u32* const items = ((SP_HBM SpWork*)W)->items;
-    for (int i = tid; i < n_items; i += stride) sp_l0_score(Tb, W, X, items[i], i);
+    for (int i = tid; i < n_items; i += stride) sp_l0_score(W, R, items[i], i);
 }
 
 template <int J, int N, class F>
@@ -2476,7 +2516,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                     __syncthreads();
                     const long long t_2a = wall_clock64();
                     const int n_items = min(X.n_items, SP_ITEMS);
-                    if ((tid & ~63) < n_items) sp_l0_score_all(c_mj_tables, W, &X, n_items, tid, NT);  // (a wavefront without items: no call)
+                    if ((tid & ~63) < n_items) sp_l0_score_all(W, &X, n_items, tid, NT);  // (a wavefront without items: no call)
                     __syncthreads();
                     if (P.prof && tid == 0) {  // level-0 sub-phases: probe, scoring (the sum is the rest of the level-0 timer)
                         X.pt[7] += (unsigned long long)(t_2a - t_2);
