@@ -3,6 +3,10 @@
  * Plain C: pointers and sizes only, no torch / C++ types.  Device pointers are raw HIP device addresses
  * (e.g. torch.Tensor.data_ptr()); `stream` is a hipStream_t passed as void* (0 = default stream).
  * Every function returns 0 on success or a negative code; mj_last_error() describes the failure.
+ * A call that returns an error leaves the pool as it was before the call: nothing of a half-done call stays behind, and the
+ * same call may be tried again.  (What a stream reports at a synchronise is a failure of work already queued on the device: the
+ * host side of the pool is as it was, the tables are not.)  One exception: mj_pool_enable_log frees the old log before it
+ * allocates the new one (a log may take a gigabyte) and on failure leaves the log disabled.
  *
  * Each entry point names the reference interface it replaces (paths relative to libriichi/src):
  *

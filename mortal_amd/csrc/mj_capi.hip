@@ -1,17 +1,21 @@
 // C-ABI host side (include/mortal_amd.h): pool life-cycle and kernel launches.  One translation unit for the whole
 // library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip.
 // Host float math below builds bit-exact LUTs: compile with -ffp-contract=off.
+// Ownership: whatever the host takes from the HIP runtime is held by an owner of mj_host.h and released by its destructor; a call that
+// returns an error leaves the pool as it was before the call (a fallible call builds into locals and moves them in as its last step).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <optional>
 #include <string>
 #include <vector>
 
 #include "../../include/mortal_amd.h"
+#include "mj_host.h"
 #include "mj_step.hip"
 #include "mj_replay.hip"
 #include "mj_encode.hip"
@@ -76,17 +80,6 @@ __global__ __launch_bounds__(64) void mj_k_algo_query(const MjAlgoQuery* q, int 
 
 namespace {
 
-thread_local std::string g_err;
-int fail(const std::string& msg) {
-    g_err = msg;
-    return -1;
-}
-#define HIP_OK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct DevTables {
     bool ready = false;
     int device = -1;  // the HIP device the tables (and the __constant__ copy of their pointers) live on
@@ -100,6 +93,13 @@ struct DevTables {
 template <class T> int upload(const std::vector<T>& v, T** out) {
     HIP_OK(hipMalloc(out, v.size() * sizeof(T)));
     HIP_OK(hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// device copy of a host array of one mj_stat_logs / mj_pool_stat call (an empty one still gets an address)
+template <class T> int stat_upload(DevBuf<T>& b, const T* src, size_t count, hipStream_t s) {
+    if (b.alloc(std::max(count, 8 / sizeof(T)))) return -1;
+    if (count) HIP_OK(hipMemcpyAsync(b.get(), src, count * sizeof(T), hipMemcpyHostToDevice, s));
     return 0;
 }
 
@@ -170,61 +170,55 @@ PoolKnobs read_knobs() {
 // HIP event pairs around timed launches, owned by a pool: pairs[0, n_pending) wait for collect(), the rest are free.  A launch
 // that fails between begin() and end() leaves its pair free.
 struct EventTimer {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;
+    std::vector<std::pair<Event, Event>> pairs;
     size_t n_pending = 0;
     int begin(hipStream_t s) {
         if (n_pending == pairs.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
-                if (a) hipEventDestroy(a);
-                return fail("hipEventCreate failed");
-            }
-            pairs.push_back({a, b});
+            Event a, b;
+            if (a.create() || b.create()) return -1;
+            pairs.emplace_back(std::move(a), std::move(b));
         }
-        HIP_OK(hipEventRecord(pairs[n_pending].first, s));
+        HIP_OK(hipEventRecord(pairs[n_pending].first.get(), s));
         return 0;
     }
     int end(hipStream_t s) {
-        HIP_OK(hipEventRecord(pairs[n_pending++].second, s));
+        HIP_OK(hipEventRecord(pairs[n_pending++].second.get(), s));
         return 0;
     }
     void collect(double* total_ms, int64_t* launches) {  // the launches timed since the last call; their pairs become free
         double tot = 0;
         for (size_t i = 0; i < n_pending; i++) {
-            hipEventSynchronize(pairs[i].second);
+            hipEventSynchronize(pairs[i].second.get());
             float ms = 0;
-            hipEventElapsedTime(&ms, pairs[i].first, pairs[i].second);
+            hipEventElapsedTime(&ms, pairs[i].first.get(), pairs[i].second.get());
             tot += ms;
         }
         if (total_ms) *total_ms = tot;
         if (launches) *launches = (int64_t)n_pending;
         n_pending = 0;
     }
-    ~EventTimer() {
-        for (auto& e : pairs) hipEventDestroy(e.first), hipEventDestroy(e.second);
-    }
 };
 
-struct SpResources {
-    SpWork* work = nullptr;     // grid areas (one per workgroup of mj_k_sp) + spare + wide_areas
+struct SpResources {  // built by sp_setup, moved into the pool whole
+    DevBuf<SpWork> work;        // grid areas (one per workgroup of mj_k_sp) + spare + wide_areas
     int grid = 0;               // mj_k_sp's largest grid
     int spare = 0;              // spare work areas = promotions per launch (small pools: mj_sp.hip "promotion"; 0 = this pool never promotes)
     int wide_areas = 0;         // work areas of mj_k_sp_wide's own workgroups (= its largest grid)
-    int* queue = nullptr;       // [0] row queue head, [1..8] / [9..16] class counts / cursors of the row sort, [SP_Q_TAIL] head of the tail
-    uint32_t* order = nullptr;  // [max_rows] queue position -> row
-    uint8_t* cls = nullptr;     // [max_rows] cost class of a row
-    unsigned long long* err = nullptr;  // [SP_ERR_WORDS] counter words (mj_sp.hip SpErrWord)
-    hipStream_t stream2 = nullptr;      // mj_k_sp_promo's stream while mj_k_sp_wide runs on the caller's (spare > 0)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    unsigned long long* gaveup_host = nullptr;  // pinned: the device's count of wide workgroups that gave up waiting, copied behind every sweep
-    void release() {
-        hipFree(work); hipFree(queue); hipFree(order); hipFree(cls); hipFree(err);
-        if (stream2) hipStreamDestroy(stream2);
-        if (ev_fork) hipEventDestroy(ev_fork);
-        if (ev_join) hipEventDestroy(ev_join);
-        if (gaveup_host) hipHostFree(gaveup_host);
-        *this = SpResources();
-    }
+    DevBuf<int> queue;          // [0] row queue head, [1..8] / [9..16] class counts / cursors of the row sort, [SP_Q_TAIL] head of the tail
+    DevBuf<uint32_t> order;     // [max_rows] queue position -> row
+    DevBuf<uint8_t> cls;        // [max_rows] cost class of a row
+    DevBuf<unsigned long long> err;     // [SP_ERR_WORDS] counter words (mj_sp.hip SpErrWord)
+    Stream stream2;                     // mj_k_sp_promo's stream while mj_k_sp_wide runs on the caller's (spare > 0)
+    Event ev_fork, ev_join;
+    PinnedBuf<unsigned long long> gaveup_host;  // the device's count of wide workgroups that gave up waiting, copied behind every sweep
+};
+
+struct ReplayBufs {  // log replay (dataset loader): built by mj_replay_load, moved into the pool whole
+    DevBuf<uint64_t> script;
+    DevBuf<uint32_t> off, cursor, ev_index;
+    DevBuf<uint8_t> kyoku, tracked;
+    DevBuf<int32_t> label, kan_label;
+    int always_kan = 1;
 };
 
 std::vector<MjGatherEnt> build_gather() {
@@ -242,22 +236,16 @@ std::vector<MjGatherEnt> build_gather() {
 
 struct MjPool {
     int n_tables = 0, n_blocks = 0, deal_algo = 0, max_rows = 0;
-    // log replay (dataset loader)
-    uint64_t* rp_script = nullptr;
-    uint32_t *rp_off = nullptr, *rp_cursor = nullptr, *rp_ev_index = nullptr;
-    uint8_t *rp_kyoku = nullptr, *rp_tracked = nullptr;
-    int32_t *rp_label = nullptr, *rp_kan_label = nullptr;
-    int rp_always_kan = 1;
+    ReplayBufs rp;
     bool rp_active = false;    // replay mode: the invisible obs lists every undrawn yama tile
-    uint64_t* log = nullptr;   // optional event log [n_tables][log_cap]
-    uint32_t* log_len = nullptr;
+    DevBuf<uint64_t> log;      // optional event log [n_tables][log_cap]
+    DevBuf<uint32_t> log_len;
     uint32_t log_cap = 0;
     int version[2] = {4, 4};  // obs version per agent (engine.version, agent/mortal.rs:57)
-    TableBlock* blocks = nullptr;
-    uint32_t* rows[2] = {nullptr, nullptr};
-    int* n_rows_dev = nullptr;
-    int* block_rows = nullptr;
-    TableOne* snap = nullptr;
+    DevBuf<TableBlock> blocks;
+    DevBuf<uint32_t> rows[2];
+    DevBuf<int> n_rows_dev, block_rows;
+    DevBuf<TableOne> snap;
     PoolKnobs knobs;
     SpResources sp;                 // allocated at the first obs-v4 encode (sp_setup)
     int sp_wide_mode = -1;          // -1 auto (launches of at most sp_wide_max_rows rows), 0 never, 1 always
@@ -265,14 +253,14 @@ struct MjPool {
     uint64_t sp_hybrid_launches = 0;
     bool sp_wide_off = false;       // the two kernels did not overlap on this system: the schedule switched itself off (see sp_launch)
     bool sp_sched_set = false;      // mj_pool_set_sp_schedule was called: the environment does not override it
-    int* enc_flag = nullptr;        // [1] an encoder op list overflowed (reported with the SP overflows)
-    int* n_rows_host = nullptr;  // pinned
-    hipEvent_t ev_rows = nullptr;  // recorded right after the row counts' copy: mj_rows_count waits for it, not for the snapshot behind it
-    hipEvent_t ev_snap = nullptr;  // recorded after mj_k_snapshot: a reader of P->snap on ANOTHER stream than the step's waits for it
+    DevBuf<int> enc_flag;           // [1] an encoder op list overflowed (reported with the SP overflows)
+    PinnedBuf<int> n_rows_host;
+    Event ev_rows;  // recorded right after the row counts' copy: mj_rows_count waits for it, not for the snapshot behind it
+    Event ev_snap;  // recorded after mj_k_snapshot: a reader of P->snap on ANOTHER stream than the step's waits for it
     hipStream_t step_stream = nullptr;  // the stream the last mj_step / mj_table_* launched on
-    unsigned long long* counters = nullptr;
-    int* final_scores = nullptr;
-    uint8_t* final_done = nullptr;
+    DevBuf<unsigned long long> counters;
+    DevBuf<int> final_scores;
+    DevBuf<uint8_t> final_done;
     int n_games_total = 0;
     int enable_quick_eval[2] = {1, 1};
     int enable_agari_guard[2] = {0, 0};
@@ -286,6 +274,19 @@ struct MjPool {
     EventTimer enc_timer, sp_timer;
 };
 
+// Host image of a pool at the start of play: zeroed tables, the padding lanes of the last block inactive, the seeds if given
+static std::vector<TableBlock> fresh_blocks(const MjPool* P, const uint64_t* nonces, const uint64_t* keys) {
+    std::vector<TableBlock> host(P->n_blocks);
+    memset(host.data(), 0, host.size() * sizeof(TableBlock));
+    for (int t = P->n_tables; t < P->n_blocks * MJ_LANES; t++) host[t >> 6].flags[t & 63] = TF_INACTIVE | TF_DONE | TF_ENDED;
+    if (nonces && keys)
+        for (int t = 0; t < P->n_tables; t++) {
+            host[t >> 6].seed_nonce[t & 63] = nonces[t];
+            host[t >> 6].seed_key[t & 63] = keys[t];
+        }
+    return host;
+}
+
 extern "C" {
 
 const char* mj_last_error(void) { return g_err.c_str(); }
@@ -296,15 +297,12 @@ int mj_algo_query(const MjAlgoQuery* queries_host, int n, MjAlgoResult* results_
     if (!g_tables.ready) return fail("mj_tables_upload has not been called");
     if (n <= 0) return 0;
     if (!queries_host || !results_host) return fail("null query / result buffer");
-    struct DevBuf {  // freed on every return path
-        void* p = nullptr;
-        ~DevBuf() { if (p) hipFree(p); }
-    } bq, br;
+    DevBuf<MjAlgoQuery> bq;
+    DevBuf<MjAlgoResult> br;
     hipStream_t s = (hipStream_t)stream;
-    HIP_OK(hipMalloc(&bq.p, (size_t)n * sizeof(MjAlgoQuery)));
-    HIP_OK(hipMalloc(&br.p, (size_t)n * sizeof(MjAlgoResult)));
-    MjAlgoQuery* dq = (MjAlgoQuery*)bq.p;
-    MjAlgoResult* dr = (MjAlgoResult*)br.p;
+    if (bq.alloc(n) || br.alloc(n)) return -1;
+    MjAlgoQuery* dq = bq.get();
+    MjAlgoResult* dr = br.get();
     HIP_OK(hipMemcpyAsync(dq, queries_host, (size_t)n * sizeof(MjAlgoQuery), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(mj_k_algo_query, dim3((n + 63) / 64), dim3(64), 0, s, dq, n, dr);
     HIP_OK(hipGetLastError());
@@ -415,87 +413,52 @@ MjPool* mj_pool_create(int n_tables, int version, int deal_algo, int max_rows) {
         fail("bad n_tables / version");
         return nullptr;
     }
-    MjPool* P = new MjPool;
+    std::unique_ptr<MjPool> P(new MjPool);
     P->knobs = read_knobs();
     P->n_tables = n_tables;
     P->n_blocks = (n_tables + MJ_LANES - 1) / MJ_LANES;
     P->version[0] = P->version[1] = version;
     P->deal_algo = deal_algo;
     P->max_rows = max_rows > 0 ? max_rows : 8 * n_tables;
-    bool ok = hipMalloc(&P->blocks, (size_t)P->n_blocks * sizeof(TableBlock)) == hipSuccess &&
-              hipMalloc(&P->rows[0], (size_t)P->max_rows * 4) == hipSuccess &&
-              hipMalloc(&P->rows[1], (size_t)P->max_rows * 4) == hipSuccess &&
-              hipMalloc(&P->n_rows_dev, 2 * sizeof(int)) == hipSuccess &&
-              hipMalloc(&P->block_rows, (size_t)P->n_blocks * 2 * sizeof(int)) == hipSuccess &&
-              hipMalloc(&P->snap, (size_t)P->n_blocks * MJ_LANES * sizeof(TableOne)) == hipSuccess &&
-              hipHostMalloc(&P->n_rows_host, 2 * sizeof(int)) == hipSuccess &&
-              hipMalloc(&P->counters, 8 * sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc(&P->enc_flag, sizeof(int)) == hipSuccess && hipMemset(P->enc_flag, 0, sizeof(int)) == hipSuccess;
-    if (!ok) {
-        fail("device allocation failed");
-        mj_pool_destroy(P);
-        return nullptr;
-    }
-    hipMemset(P->blocks, 0, (size_t)P->n_blocks * sizeof(TableBlock));
+    if (P->blocks.alloc(P->n_blocks) || P->rows[0].alloc(P->max_rows) || P->rows[1].alloc(P->max_rows) || P->n_rows_dev.alloc(2) ||
+        P->block_rows.alloc((size_t)P->n_blocks * 2) || P->snap.alloc((size_t)P->n_blocks * MJ_LANES) || P->n_rows_host.alloc(2) ||
+        P->counters.alloc(8) || P->enc_flag.alloc(1))
+        return nullptr;  // (~MjPool releases what was allocated)
+    if (hipMemset(P->enc_flag.get(), 0, sizeof(int)) != hipSuccess) return fail("hipMemset of the encoder's overflow flag failed"), nullptr;
+    hipMemset(P->blocks.get(), 0, (size_t)P->n_blocks * sizeof(TableBlock));
     for (int v = 1; v <= 4; v++) {
         const void* fn = v == 1 ? (const void*)mj_k_encode<1> : v == 2 ? (const void*)mj_k_encode<2>
                        : v == 3 ? (const void*)mj_k_encode<3> : (const void*)mj_k_encode<4>;
         hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds_bytes(v, P->knobs.enc_lds_pad));
     }
-    return P;
+    return P.release();
 }
 
-void mj_pool_destroy(MjPool* P) {
-    if (!P) return;
-    hipFree(P->blocks);
-    hipFree(P->rows[0]);
-    hipFree(P->rows[1]);
-    hipFree(P->n_rows_dev);
-    hipFree(P->block_rows);
-    hipFree(P->snap);
-    P->sp.release();
-    hipFree(P->enc_flag);
-    hipFree(P->log);
-    hipFree(P->log_len);
-    hipFree(P->rp_script); hipFree(P->rp_off); hipFree(P->rp_cursor); hipFree(P->rp_ev_index);
-    hipFree(P->rp_kyoku); hipFree(P->rp_tracked); hipFree(P->rp_label); hipFree(P->rp_kan_label);
-    if (P->n_rows_host) hipHostFree(P->n_rows_host);
-    if (P->ev_rows) hipEventDestroy(P->ev_rows);
-    if (P->ev_snap) hipEventDestroy(P->ev_snap);
-    hipFree(P->counters);
-    hipFree(P->final_scores);
-    hipFree(P->final_done);
-    delete P;  // (the timing events: ~EventTimer)
-}
+void mj_pool_destroy(MjPool* P) { delete P; }
 
 int mj_pool_reset(MjPool* P, const uint64_t* nonces, const uint64_t* keys, const uint32_t* game_ids,
                   const uint8_t* agent_of_seat, int n_games_total) {
     if (!P) return fail("null pool");
-    std::vector<TableBlock> host(P->n_blocks);
-    memset(host.data(), 0, host.size() * sizeof(TableBlock));
-    for (int t = 0; t < P->n_blocks * MJ_LANES; t++) {
+    std::vector<TableBlock> host = fresh_blocks(P, nonces, keys);
+    for (int t = 0; t < P->n_tables; t++) {
         TableBlock& B = host[t >> 6];
         int l = t & 63;
-        if (t >= P->n_tables) {
-            B.flags[l] = TF_INACTIVE | TF_DONE | TF_ENDED;
-            continue;
-        }
-        B.seed_nonce[l] = nonces[t];
-        B.seed_key[l] = keys[t];
         B.game_id[l] = game_ids ? game_ids[t] : (uint32_t)t;
         B.agent_of_seat[l] = agent_of_seat ? agent_of_seat[t] : 0;
         for (int i = 0; i < 4; i++) B.scores[i][l] = 25000;  // BatchGame::tenhou_hanchan (game.rs:222-228)
     }
-    HIP_OK(hipMemcpy(P->blocks, host.data(), host.size() * sizeof(TableBlock), hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(P->counters, 0, 8 * sizeof(unsigned long long)));
-    hipFree(P->final_scores);
-    hipFree(P->final_done);
-    P->n_games_total = n_games_total > 0 ? n_games_total : P->n_tables;
-    HIP_OK(hipMalloc(&P->final_scores, (size_t)P->n_games_total * 4 * sizeof(int)));
-    HIP_OK(hipMalloc(&P->final_done, (size_t)P->n_games_total));
-    HIP_OK(hipMemset(P->final_scores, 0, (size_t)P->n_games_total * 4 * sizeof(int)));
-    HIP_OK(hipMemset(P->final_done, 0, (size_t)P->n_games_total));
-    if (P->log_len) HIP_OK(hipMemset(P->log_len, 0, (size_t)P->n_tables * sizeof(uint32_t)));
+    const int n_games = n_games_total > 0 ? n_games_total : P->n_tables;
+    DevBuf<int> final_scores;
+    DevBuf<uint8_t> final_done;
+    if (final_scores.alloc((size_t)n_games * 4) || final_done.alloc(n_games)) return -1;
+    HIP_OK(hipMemset(final_scores.get(), 0, (size_t)n_games * 4 * sizeof(int)));
+    HIP_OK(hipMemset(final_done.get(), 0, (size_t)n_games));
+    HIP_OK(hipMemcpy(P->blocks.get(), host.data(), host.size() * sizeof(TableBlock), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(P->counters.get(), 0, 8 * sizeof(unsigned long long)));
+    if (P->log_len) HIP_OK(hipMemset(P->log_len.get(), 0, (size_t)P->n_tables * sizeof(uint32_t)));
+    P->final_scores = std::move(final_scores);  // (the previous pair goes with the locals)
+    P->final_done = std::move(final_done);
+    P->n_games_total = n_games;
     P->rp_active = false;
     P->cycles = 0;
     P->start_stagger = 0;
@@ -505,25 +468,32 @@ int mj_pool_reset(MjPool* P, const uint64_t* nonces, const uint64_t* keys, const
 
 int mj_pool_enable_log(MjPool* P, uint32_t words_per_table) {
     if (!P) return fail("null pool");
-    if (P->log) { hipFree(P->log); hipFree(P->log_len); P->log = nullptr; P->log_len = nullptr; }
-    P->log_cap = words_per_table;
+    // The one exception to "an error leaves the pool as it was": the log may take a gigabyte, so the old one goes first and a failure
+    // leaves the log disabled.
+    P->log.reset();
+    P->log_len.reset();
+    P->log_cap = 0;
     if (words_per_table == 0) return 0;
-    HIP_OK(hipMalloc(&P->log, (size_t)P->n_tables * words_per_table * sizeof(uint64_t)));
-    HIP_OK(hipMalloc(&P->log_len, (size_t)P->n_tables * sizeof(uint32_t)));
-    HIP_OK(hipMemset(P->log_len, 0, (size_t)P->n_tables * sizeof(uint32_t)));
+    DevBuf<uint64_t> log;
+    DevBuf<uint32_t> log_len;
+    if (log.alloc((size_t)P->n_tables * words_per_table) || log_len.alloc(P->n_tables)) return -1;
+    HIP_OK(hipMemset(log_len.get(), 0, (size_t)P->n_tables * sizeof(uint32_t)));
+    P->log = std::move(log);
+    P->log_len = std::move(log_len);
+    P->log_cap = words_per_table;
     return 0;
 }
 int mj_log_lengths(MjPool* P, uint32_t* len_out, void* stream) {
     if (!P || !P->log) return fail("event log is not enabled");
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    HIP_OK(hipMemcpy(len_out, P->log_len, (size_t)P->n_tables * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(len_out, P->log_len.get(), (size_t)P->n_tables * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 int mj_log_read(MjPool* P, int table0, int n, uint64_t* words_out, void* stream) {
     if (!P || !P->log) return fail("event log is not enabled");
     if (table0 < 0 || n < 0 || table0 + n > P->n_tables) return fail("table range out of bounds");
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    HIP_OK(hipMemcpy(words_out, P->log + (size_t)table0 * P->log_cap, (size_t)n * P->log_cap * sizeof(uint64_t),
+    HIP_OK(hipMemcpy(words_out, P->log.get() + (size_t)table0 * P->log_cap, (size_t)n * P->log_cap * sizeof(uint64_t),
                      hipMemcpyDeviceToHost));
     return 0;
 }
@@ -550,7 +520,7 @@ int mj_pool_set_start_stagger(MjPool* P, uint32_t cycles, void* stream) {
     if (cycles && !P->refill_stride) return fail("mj_pool_set_start_stagger needs the refill mode (mj_pool_set_refill)");
     if (!cycles && P->start_stagger) return fail("mj_pool_set_start_stagger(0) after the tables were parked: reset the pool instead");
     P->start_stagger = cycles;
-    if (cycles) hipLaunchKernelGGL(mj_k_park, dim3(P->n_blocks), dim3(64), 0, (hipStream_t)stream, P->blocks, P->n_tables);
+    if (cycles) hipLaunchKernelGGL(mj_k_park, dim3(P->n_blocks), dim3(64), 0, (hipStream_t)stream, P->blocks.get(), P->n_tables);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -559,7 +529,7 @@ static int launch_rows(MjPool* P, hipStream_t s);
 // mj_rows_count returns as soon as the row counts are on the host; mj_k_snapshot, queued behind their copy, may still be running.  A
 // reader of the snapshot records on the SAME stream is ordered behind it by the stream; one on another stream waits for ev_snap.
 static int wait_snapshot(MjPool* P, hipStream_t s) {
-    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap, 0));
+    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));
     return 0;
 }
 int mj_step(MjPool* P, const int32_t* a0, const int32_t* a1, void* stream) {
@@ -575,7 +545,7 @@ int mj_step_ev(MjPool* P, const int32_t* a0, const int32_t* a1, const float* q0,
         return fail("enable_rule_based_agari_guard needs the q-values of the batch (mj_step_q)");
     hipStream_t s = (hipStream_t)stream;
     StepParams sp;
-    sp.blocks = P->blocks;
+    sp.blocks = P->blocks.get();
     sp.n_tables = P->n_tables;
     sp.tables = g_tables.dev;
     sp.actions[0] = a0;
@@ -584,8 +554,8 @@ int mj_step_ev(MjPool* P, const int32_t* a0, const int32_t* a1, const float* q0,
     sp.q_values[1] = q1;
     sp.reactions[0] = ev0;
     sp.reactions[1] = ev1;
-    sp.log = P->log;
-    sp.log_len = P->log_len;
+    sp.log = P->log.get();
+    sp.log_len = P->log_len.get();
     sp.log_cap = P->log_cap;
     sp.cycle = (uint32_t)P->cycles;
     sp.deal_algo = P->deal_algo;
@@ -597,36 +567,36 @@ int mj_step_ev(MjPool* P, const int32_t* a0, const int32_t* a1, const float* q0,
     sp.refill = P->refill_stride != 0;
     sp.refill_stride = P->refill_stride;
     sp.start_stagger = P->start_stagger;
-    sp.counters = P->counters;
-    sp.final_scores = P->final_scores;
-    sp.final_done = P->final_done;
+    sp.counters = P->counters.get();
+    sp.final_scores = P->final_scores.get();
+    sp.final_done = P->final_done.get();
     sp.n_games_total = P->n_games_total;
-    sp.block_rows = P->block_rows;
+    sp.block_rows = P->block_rows.get();
     if (sp.refill) hipLaunchKernelGGL(mj_k_refill, dim3(P->n_blocks), dim3(64), 0, s, sp);
     hipLaunchKernelGGL(mj_k_step, dim3(P->n_blocks), dim3(MJ_LANES), 0, s, sp);
     return launch_rows(P, s);
 }
 static int launch_rows(MjPool* P, hipStream_t s) {
     RowsParams rp;
-    rp.blocks = P->blocks;
+    rp.blocks = P->blocks.get();
     rp.n_blocks = P->n_blocks;
-    rp.block_rows = P->block_rows;
-    rp.rows[0] = P->rows[0];
-    rp.rows[1] = P->rows[1];
-    rp.n_rows_out = P->n_rows_dev;
+    rp.block_rows = P->block_rows.get();
+    rp.rows[0] = P->rows[0].get();
+    rp.rows[1] = P->rows[1].get();
+    rp.n_rows_out = P->n_rows_dev.get();
     rp.max_rows[0] = rp.max_rows[1] = P->max_rows;
     hipLaunchKernelGGL(mj_k_scan, dim3(1), dim3(1024), 0, s, rp);
     hipLaunchKernelGGL(mj_k_assign, dim3(P->n_blocks), dim3(64), 0, s, rp);
     // the row counts go to the host BEFORE the snapshot is queued (round 5): the host's read of them (mj_rows_count, one per cycle) and
     // its launch of the encoder then run under the snapshot kernel's 0.1 ms instead of after it
-    HIP_OK(hipMemcpyAsync(P->n_rows_host, P->n_rows_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (!P->ev_rows) HIP_OK(hipEventCreateWithFlags(&P->ev_rows, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(P->ev_rows, s));
-    SnapParams snp = {P->blocks, P->snap, g_tables.gather, {0}};
+    HIP_OK(hipMemcpyAsync(P->n_rows_host.get(), P->n_rows_dev.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (!P->ev_rows && P->ev_rows.create_no_timing()) return -1;
+    HIP_OK(hipEventRecord(P->ev_rows.get(), s));
+    SnapParams snp = {P->blocks.get(), P->snap.get(), g_tables.gather, {0}};
     for (int c = 0; c <= SNAP_NCH; c++) snp.chunk_first[c] = g_tables.gather_chunk[c];
     hipLaunchKernelGGL(mj_k_snapshot, dim3(P->n_blocks), dim3(256), 0, s, snp);
-    if (!P->ev_snap) HIP_OK(hipEventCreateWithFlags(&P->ev_snap, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(P->ev_snap, s));
+    if (!P->ev_snap && P->ev_snap.create_no_timing()) return -1;
+    HIP_OK(hipEventRecord(P->ev_snap.get(), s));
     P->step_stream = s;
     HIP_OK(hipGetLastError());
     P->cycles += 1;
@@ -640,66 +610,54 @@ int mj_replay_load(MjPool* P, const uint64_t* script, const uint32_t* off, const
     if (!P) return fail("null pool");
     if (n_logs != P->n_tables) return fail("mj_replay_load: one log per table (create the pool with n_tables = n_logs)");
     const size_t n_words = off[n_logs];
-    hipFree(P->rp_script); hipFree(P->rp_off); hipFree(P->rp_cursor); hipFree(P->rp_ev_index);
-    hipFree(P->rp_kyoku); hipFree(P->rp_tracked); hipFree(P->rp_label); hipFree(P->rp_kan_label);
-    HIP_OK(hipMalloc(&P->rp_script, (n_words + 1) * sizeof(uint64_t)));
-    HIP_OK(hipMalloc(&P->rp_off, (size_t)(n_logs + 1) * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&P->rp_cursor, (size_t)n_logs * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&P->rp_ev_index, (size_t)n_logs * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&P->rp_kyoku, (size_t)n_logs));
-    HIP_OK(hipMalloc(&P->rp_tracked, (size_t)n_logs));
-    HIP_OK(hipMalloc(&P->rp_label, (size_t)n_logs * 4 * sizeof(int32_t)));
-    HIP_OK(hipMalloc(&P->rp_kan_label, (size_t)n_logs * 4 * sizeof(int32_t)));
-    HIP_OK(hipMemcpy(P->rp_script, script, n_words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(P->rp_off, off, (size_t)(n_logs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(P->rp_tracked, tracked, (size_t)n_logs, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(P->rp_cursor, 0, (size_t)n_logs * sizeof(uint32_t)));
-    HIP_OK(hipMemset(P->rp_ev_index, 0, (size_t)n_logs * sizeof(uint32_t)));
-    HIP_OK(hipMemset(P->rp_kyoku, 0, (size_t)n_logs));
-    P->rp_always_kan = always_include_kan_select;
-    // fresh tables (all seats agent 0); padding lanes of the last block inactive
-    std::vector<TableBlock> host(P->n_blocks);
-    memset(host.data(), 0, host.size() * sizeof(TableBlock));
-    for (int t = P->n_tables; t < P->n_blocks * MJ_LANES; t++) host[t >> 6].flags[t & 63] = TF_INACTIVE | TF_DONE | TF_ENDED;
-    if (nonces && keys)
-        for (int t = 0; t < P->n_tables; t++) {
-            host[t >> 6].seed_nonce[t & 63] = nonces[t];
-            host[t >> 6].seed_key[t & 63] = keys[t];
-        }
+    ReplayBufs R;
+    if (R.script.alloc(n_words + 1) || R.off.alloc((size_t)n_logs + 1) || R.cursor.alloc(n_logs) || R.ev_index.alloc(n_logs) ||
+        R.kyoku.alloc(n_logs) || R.tracked.alloc(n_logs) || R.label.alloc((size_t)n_logs * 4) || R.kan_label.alloc((size_t)n_logs * 4))
+        return -1;
+    HIP_OK(hipMemcpy(R.script.get(), script, n_words * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(R.off.get(), off, (size_t)(n_logs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(R.tracked.get(), tracked, (size_t)n_logs, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(R.cursor.get(), 0, (size_t)n_logs * sizeof(uint32_t)));
+    HIP_OK(hipMemset(R.ev_index.get(), 0, (size_t)n_logs * sizeof(uint32_t)));
+    HIP_OK(hipMemset(R.kyoku.get(), 0, (size_t)n_logs));
+    R.always_kan = always_include_kan_select;
+    std::vector<TableBlock> host = fresh_blocks(P, nonces, keys);  // fresh tables (all seats agent 0)
+    HIP_OK(hipMemcpy(P->blocks.get(), host.data(), host.size() * sizeof(TableBlock), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(P->counters.get(), 0, 8 * sizeof(unsigned long long)));
+    P->rp = std::move(R);  // (buffers of an earlier load go with R)
     P->rp_active = true;
-    HIP_OK(hipMemcpy(P->blocks, host.data(), host.size() * sizeof(TableBlock), hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(P->counters, 0, 8 * sizeof(unsigned long long)));
     P->cycles = 0;
     P->rows_valid = false;
     return 0;
 }
 int mj_replay_step(MjPool* P, void* stream) {
-    if (!P || !P->rp_script) return fail("mj_replay_load first");
+    if (!P || !P->rp.script) return fail("mj_replay_load first");
     ReplayParams rp;
-    rp.blocks = P->blocks;
+    rp.blocks = P->blocks.get();
     rp.n_tables = P->n_tables;
-    rp.script = P->rp_script;
-    rp.script_off = P->rp_off;
-    rp.cursor = P->rp_cursor;
-    rp.ev_index = P->rp_ev_index;
-    rp.kyoku_idx = P->rp_kyoku;
-    rp.tracked = P->rp_tracked;
-    rp.always_include_kan_select = P->rp_always_kan;
+    rp.script = P->rp.script.get();
+    rp.script_off = P->rp.off.get();
+    rp.cursor = P->rp.cursor.get();
+    rp.ev_index = P->rp.ev_index.get();
+    rp.kyoku_idx = P->rp.kyoku.get();
+    rp.tracked = P->rp.tracked.get();
+    rp.always_include_kan_select = P->rp.always_kan;
     rp.deal_algo = P->deal_algo;
-    rp.block_rows = P->block_rows;
-    rp.label = P->rp_label;
-    rp.kan_label = P->rp_kan_label;
-    rp.counters = P->counters;
+    rp.block_rows = P->block_rows.get();
+    rp.label = P->rp.label.get();
+    rp.kan_label = P->rp.kan_label.get();
+    rp.counters = P->counters.get();
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(mj_k_replay, dim3(P->n_blocks), dim3(64), 0, s, rp);
     return launch_rows(P, s);
 }
 int mj_replay_meta(MjPool* P, int32_t* meta_dev, void* stream) {
-    if (!P || !P->rp_script) return fail("mj_replay_load first");
+    if (!P || !P->rp.script) return fail("mj_replay_load first");
     if (!P->rows_valid) return fail("mj_rows_count must be called after mj_replay_step");
     const int n = P->last_rows[0];
     if (n == 0) return 0;
-    ReplayMetaParams mp = {P->blocks, P->rows[0], n, P->rp_label, P->rp_kan_label, P->rp_kyoku, P->rp_ev_index, meta_dev};
+    ReplayMetaParams mp = {P->blocks.get(), P->rows[0].get(), n, P->rp.label.get(), P->rp.kan_label.get(), P->rp.kyoku.get(),
+                           P->rp.ev_index.get(), meta_dev};
     hipLaunchKernelGGL(mj_k_replay_meta, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, mp);
     HIP_OK(hipGetLastError());
     return 0;
@@ -710,43 +668,42 @@ int mj_table_apply_event(MjPool* P, int table, const uint64_t* words, int n_word
     if (!P || table < 0 || table >= P->n_tables) return fail("bad table");
     if (n_words < 1 || n_words > 16) return fail("bad event");
     hipStream_t s = (hipStream_t)stream;
-    uint64_t* dev = nullptr;
-    HIP_OK(hipMalloc(&dev, 16 * sizeof(uint64_t)));
-    HIP_OK(hipMemcpyAsync(dev, words, (size_t)n_words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(mj_k_apply_event, dim3(1), dim3(1), 0, s, P->blocks, table, dev);
+    DevBuf<uint64_t> dev;
+    if (dev.alloc(16)) return -1;
+    HIP_OK(hipMemcpyAsync(dev.get(), words, (size_t)n_words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(mj_k_apply_event, dim3(1), dim3(1), 0, s, P->blocks.get(), table, dev.get());
     HIP_OK(hipStreamSynchronize(s));
-    hipFree(dev);
     HIP_OK(hipGetLastError());
     return 0;
 }
 int mj_table_mark_row(MjPool* P, int table, int seat, int at_kan_select, void* stream) {
     if (!P || table < 0 || table >= P->n_tables || seat < 0 || seat > 3) return fail("bad table / seat");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(mj_k_mark_row, dim3(P->n_blocks), dim3(64), 0, s, P->blocks, P->n_tables, table, seat, at_kan_select,
-                       P->block_rows);
+    hipLaunchKernelGGL(mj_k_mark_row, dim3(P->n_blocks), dim3(64), 0, s, P->blocks.get(), P->n_tables, table, seat,
+                       at_kan_select, P->block_rows.get());
     return launch_rows(P, s);
 }
 int mj_table_query(MjPool* P, int table, int seat, int what, const int32_t* args8, int32_t* out8, void* stream) {
     if (!P || table < 0 || table >= P->n_tables || seat < 0 || seat > 3) return fail("bad table / seat");
     hipStream_t s = (hipStream_t)stream;
-    int32_t* dev = nullptr;
-    HIP_OK(hipMalloc(&dev, 16 * sizeof(int32_t)));
+    DevBuf<int32_t> buf;
+    if (buf.alloc(16)) return -1;
+    int32_t* dev = buf.get();
     HIP_OK(hipMemsetAsync(dev, 0, 16 * sizeof(int32_t), s));
     if (args8) HIP_OK(hipMemcpyAsync(dev, args8, 8 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(mj_k_query, dim3(1), dim3(1), 0, s, P->blocks, table, seat, what, dev, dev + 8);
+    hipLaunchKernelGGL(mj_k_query, dim3(1), dim3(1), 0, s, P->blocks.get(), table, seat, what, dev, dev + 8);
     HIP_OK(hipMemcpyAsync(out8, dev + 8, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    hipFree(dev);
     HIP_OK(hipGetLastError());
     return 0;
 }
 
 int mj_rows_count(MjPool* P, int32_t out[2], void* stream) {
     if (!P) return fail("null pool");
-    if (P->ev_rows) HIP_OK(hipEventSynchronize(P->ev_rows));  // (the counts' copy; the snapshot queued behind it may still be running)
+    if (P->ev_rows) HIP_OK(hipEventSynchronize(P->ev_rows.get()));  // (the counts' copy; the snapshot queued behind it may still be running)
     else HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    out[0] = P->n_rows_host[0];
-    out[1] = P->n_rows_host[1];
+    out[0] = P->n_rows_host.get()[0];
+    out[1] = P->n_rows_host.get()[1];
     // a batch that does not fit rows[] stays invalid (rows_valid false, last_rows never above max_rows): mj_encode, mj_encode_oracle
     // and mj_replay_meta refuse it with their "mj_rows_count must be called" error instead of walking rows[] past its allocation
     if (out[0] > P->max_rows || out[1] > P->max_rows) return fail("row capacity exceeded");
@@ -755,107 +712,102 @@ int mj_rows_count(MjPool* P, int32_t out[2], void* stream) {
     P->rows_valid = true;
     return 0;
 }
-const uint32_t* mj_rows_dev(MjPool* P, int agent) { return P ? P->rows[agent & 1] : nullptr; }
+const uint32_t* mj_rows_dev(MjPool* P, int agent) { return P ? P->rows[agent & 1].get() : nullptr; }
 
-static SpParams sp_params(const MjPool* P, int agent, float* obs, int n) {
+static SpParams sp_params(const MjPool* P, const SpResources& R, int agent, float* obs, int n) {
     SpParams kp{};
-    kp.snap = P->snap;
-    kp.rows = P->rows[agent & 1];
+    kp.snap = P->snap.get();
+    kp.rows = P->rows[agent & 1].get();
     kp.n_rows = n;
     kp.tables = g_tables.dev;
     kp.obs = obs;
-    kp.work = P->sp.work;
-    kp.queue = P->sp.queue;
-    kp.order = P->sp.order;
-    kp.err = P->sp.err;
+    kp.work = R.work.get();
+    kp.queue = R.queue.get();
+    kp.order = R.order.get();
+    kp.err = R.err.get();
     return kp;
 }
 
 // The SP kernels' resources, sized at the pool's first obs-v4 encode (mj_pool_set_sp_schedule may change the mode until then).
-// All or nothing: after a failure the pool is as it was, and the next v4 encode tries again.
+// All or nothing: they are built in a local and moved into the pool last, so after a failure the next v4 encode tries again.
 static int sp_setup(MjPool* P, int agent, float* obs, hipStream_t s) {
-    SpResources& R = P->sp;
+    SpResources R;
     const PoolKnobs& K = P->knobs;
-    struct Undo {  // releases whatever was allocated on every early return
-        SpResources* R;
-        ~Undo() { if (R) R->release(); }
-    } undo{&R};
-    HIP_OK(hipMalloc(&R.err, SP_ERR_WORDS * sizeof(unsigned long long)));
-    HIP_OK(hipMemset(R.err, 0, SP_ERR_WORDS * sizeof(unsigned long long)));
-    HIP_OK(hipMalloc(&R.order, (size_t)P->max_rows * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&R.cls, (size_t)P->max_rows));
+    if (R.err.alloc(SP_ERR_WORDS)) return -1;
+    HIP_OK(hipMemset(R.err.get(), 0, SP_ERR_WORDS * sizeof(unsigned long long)));
+    if (R.order.alloc(P->max_rows) || R.cls.alloc(P->max_rows)) return -1;
     // persistent workgroups: SP_WGS per CU, one decision row each at a time; never more than the rows of a launch (small pools: small work area)
     R.grid = std::min(256 * SP_WGS, P->max_rows);
     if (K.sp_grid) R.grid = std::max(1, std::min(R.grid, *K.sp_grid));
-    if (!P->sp_sched_set) {
-        if (K.sp_wide) P->sp_wide_mode = *K.sp_wide;
-        if (K.sp_wide_max_rows) P->sp_wide_max_rows = *K.sp_wide_max_rows;
-        if (K.sp_wide_grid) P->sp_wide_grid = std::max(1, *K.sp_wide_grid);
-        if (K.sp_promo_min1) P->sp_promo_min[1] = std::max(1, *K.sp_promo_min1);
-        if (K.sp_promo_min2) P->sp_promo_min[2] = std::max(1, *K.sp_promo_min2);
-    }
-    R.spare = P->sp_wide_mode == 0 ? 0 : std::min(SP_PROMO_CAP, std::max(8, P->n_tables / 4) & ~1);
-    if (P->sp_wide_mode < 0 && P->n_tables > P->sp_wide_max_rows) R.spare = 0;  // (a launch has about as many rows as the pool has tables)
+    const bool env = !P->sp_sched_set;  // the environment's schedule applies (to the pool: with the resources, below)
+    const int wide_mode = env && K.sp_wide ? *K.sp_wide : P->sp_wide_mode;
+    const int wide_max_rows = env && K.sp_wide_max_rows ? *K.sp_wide_max_rows : P->sp_wide_max_rows;
+    R.spare = wide_mode == 0 ? 0 : std::min(SP_PROMO_CAP, std::max(8, P->n_tables / 4) & ~1);
+    if (wide_mode < 0 && P->n_tables > wide_max_rows) R.spare = 0;  // (a launch has about as many rows as the pool has tables)
     R.wide_areas = R.spare ? std::min(256, std::max(2, P->n_tables / 16)) : 0;  // (a 64-table test pool does not need 2 GB of work areas)
     const int areas = R.grid + R.spare + R.wide_areas;
-    HIP_OK(hipMalloc(&R.work, (size_t)areas * sizeof(SpWork)));
+    if (R.work.alloc(areas)) return -1;
     for (int g = 0; g < areas; g++) {
-        HIP_OK(hipMemsetAsync(R.work[g].tag, 0, sizeof(R.work[g].tag), s));  // empty hash sets ...
-        HIP_OK(hipMemsetAsync(&R.work[g].epoch, 0, sizeof(R.work[g].epoch) + sizeof(R.work[g].pad_), s));  // ... at epoch 0
+        SpWork& W = R.work.get()[g];
+        HIP_OK(hipMemsetAsync(W.tag, 0, sizeof(W.tag), s));  // empty hash sets ...
+        HIP_OK(hipMemsetAsync(&W.epoch, 0, sizeof(W.epoch) + sizeof(W.pad_), s));  // ... at epoch 0
     }
-    HIP_OK(hipMalloc(&R.queue, SP_Q_WORDS * sizeof(int)));
+    if (R.queue.alloc(SP_Q_WORDS)) return -1;
     if (R.spare) {
-        HIP_OK(hipStreamCreateWithFlags(&R.stream2, hipStreamNonBlocking));
-        HIP_OK(hipEventCreateWithFlags(&R.ev_fork, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&R.ev_join, hipEventDisableTiming));
-        HIP_OK(hipHostMalloc(&R.gaveup_host, sizeof(unsigned long long)));
-        *R.gaveup_host = 0ull;
+        if (R.stream2.create_non_blocking() || R.ev_fork.create_no_timing() || R.ev_join.create_no_timing() || R.gaveup_host.alloc(1)) return -1;
+        *R.gaveup_host.get() = 0ull;
         // One empty launch of the pair now: the HIP runtime sizes a queue's scratch at the first launch that needs it, and a caller
         // whose allocator has taken the whole HBM by then (torch's caching allocator under a growing batch) turns that into
         // HSA_STATUS_ERROR_OUT_OF_RESOURCES in the middle of a run -- at pool set-up it is an ordinary, early failure.
-        HIP_OK(hipMemsetAsync(R.queue, 0, SP_Q_WORDS * sizeof(int), s));
+        HIP_OK(hipMemsetAsync(R.queue.get(), 0, SP_Q_WORDS * sizeof(int), s));
         HIP_OK(hipStreamSynchronize(s));
-        SpParams w = sp_params(P, agent, obs, 0);
+        SpParams w = sp_params(P, R, agent, obs, 0);
         w.sweep = 1;
         hipLaunchKernelGGL(mj_k_sp_wide, dim3(1), dim3(SP_WIDE_THREADS), 0, s, w);
-        hipLaunchKernelGGL(mj_k_sp_promo, dim3(1), dim3(SP_THREADS), 0, R.stream2, w);
-        HIP_OK(hipStreamSynchronize(R.stream2));
+        hipLaunchKernelGGL(mj_k_sp_promo, dim3(1), dim3(SP_THREADS), 0, R.stream2.get(), w);
+        HIP_OK(hipStreamSynchronize(R.stream2.get()));
         HIP_OK(hipStreamSynchronize(s));
         HIP_OK(hipGetLastError());
     }
-    undo.R = nullptr;
+    P->sp = std::move(R);
+    P->sp_wide_mode = wide_mode;
+    P->sp_wide_max_rows = wide_max_rows;
+    if (env && K.sp_wide_grid) P->sp_wide_grid = std::max(1, *K.sp_wide_grid);
+    if (env && K.sp_promo_min1) P->sp_promo_min[1] = std::max(1, *K.sp_promo_min1);
+    if (env && K.sp_promo_min2) P->sp_promo_min[2] = std::max(1, *K.sp_promo_min2);
     return 0;
 }
 
 #ifdef SP_ROWDUMP
 // (debug) MJ_SP_ROWDUMP: the per-row cost records of every launch appended to that file, one synchronous copy per launch
-static int rowdump_begin(MjPool* P, SpParams& kp, hipStream_t s) {
-    HIP_OK(hipMalloc(&kp.rowdump, (size_t)kp.n_rows * 48));
+// (`dump` belongs to sp_launch: whatever happens in between, the records are freed when the launch returns)
+static int rowdump_begin(MjPool* P, SpParams& kp, DevBuf<uint32_t>& dump, hipStream_t s) {
+    if (dump.alloc((size_t)kp.n_rows * 12)) return -1;
+    kp.rowdump = dump.get();
     HIP_OK(hipMemsetAsync(kp.rowdump, 0, (size_t)kp.n_rows * 48, s));
-    HIP_OK(hipMemsetAsync(P->sp.err + SP_ERR_DUMP_T0, 0xFF, 8, s));
-    HIP_OK(hipMemsetAsync(P->sp.err + SP_ERR_DUMP_NARROW, 0, 24, s));
+    HIP_OK(hipMemsetAsync(P->sp.err.get() + SP_ERR_DUMP_T0, 0xFF, 8, s));
+    HIP_OK(hipMemsetAsync(P->sp.err.get() + SP_ERR_DUMP_NARROW, 0, 24, s));
     return 0;
 }
-static int rowdump_end(MjPool* P, const SpParams& kp, hipStream_t s) {
+static int rowdump_end(MjPool* P, const SpParams& kp, DevBuf<uint32_t>& dump, hipStream_t s) {
     const int n = kp.n_rows;
     std::vector<uint32_t> h((size_t)n * 12);
     int q[SP_Q_WORDS];
     HIP_OK(hipMemcpyAsync(h.data(), kp.rowdump, (size_t)n * 48, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(q, P->sp.queue, sizeof(q), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(q, P->sp.queue.get(), sizeof(q), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    hipFree(kp.rowdump);
-    if (FILE* f = fopen(P->knobs.sp_rowdump.c_str(), "ab")) {
+    dump.reset();
+    if (std::unique_ptr<FILE, int (*)(FILE*)> f{fopen(P->knobs.sp_rowdump.c_str(), "ab"), fclose}) {
         uint32_t hdr[12] = {0xFFFFFFFFu, (uint32_t)n};
         unsigned long long tt[4];
-        HIP_OK(hipMemcpy(tt, P->sp.err + SP_ERR_DUMP_T0, sizeof tt, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(tt, P->sp.err.get() + SP_ERR_DUMP_T0, sizeof tt, hipMemcpyDeviceToHost));
         for (int k = 0; k < 4; k++) hdr[2 + k] = (uint32_t)tt[k];  // first workgroup in, last narrow / wide out of the row loop, end of the tail
-        fwrite(hdr, 4, 12, f);
+        fwrite(hdr, 4, 12, f.get());
         uint32_t cc[12];
         for (int k = 0; k < 12; k++) cc[k] = k < 8 ? (uint32_t)q[1 + k] : 0u;
-        fwrite(cc, 4, 12, f);
+        fwrite(cc, 4, 12, f.get());
         for (int i = 0; i < n; i++)
-            if (h[(size_t)i * 12 + 7]) fwrite(&h[(size_t)i * 12], 4, 12, f);
-        fclose(f);
+            if (h[(size_t)i * 12 + 7]) fwrite(&h[(size_t)i * 12], 4, 12, f.get());
     }
     return 0;
 }
@@ -864,21 +816,22 @@ static int rowdump_end(MjPool* P, const SpParams& kp, hipStream_t s) {
 // One SP launch over the n rows just encoded: the row order, then mj_k_sp alone or the small-pool schedule
 static int sp_launch(MjPool* P, int agent, float* obs, int n, hipStream_t s) {
     SpResources& R = P->sp;
-    HIP_OK(hipMemsetAsync(R.queue, 0, SP_Q_WORDS * sizeof(int), s));
-    SpParams kp = sp_params(P, agent, obs, n);
-    kp.prof = P->knobs.sp_prof ? R.err : nullptr;
+    HIP_OK(hipMemsetAsync(R.queue.get(), 0, SP_Q_WORDS * sizeof(int), s));
+    SpParams kp = sp_params(P, R, agent, obs, n);
+    kp.prof = P->knobs.sp_prof ? R.err.get() : nullptr;
 #ifdef SP_ROWDUMP
-    if (!P->knobs.sp_rowdump.empty() && rowdump_begin(P, kp, s)) return -1;
+    DevBuf<uint32_t> dump;
+    if (!P->knobs.sp_rowdump.empty() && rowdump_begin(P, kp, dump, s)) return -1;
 #endif
     const int grid = std::min(n, R.grid);
     // The schedule needs mj_k_sp_wide and mj_k_sp_promo side by side.  Where they do not overlap -- more streams in the process than the
     // runtime has hardware queues, so that the promo kernel queues up BEHIND the spinning wide kernel -- the wide workgroups give up
     // after SP_WIDE_TIMEOUT, the sweep launch still produces the same obs, and the give-ups (copied to pinned memory behind every
     // sweep) switch the schedule off for this pool: one slow launch, then mj_k_sp alone as in round 5.
-    if (P->sp_wide_mode < 0 && R.gaveup_host && *R.gaveup_host && !P->sp_wide_off) {  // (auto mode only: mode 1 = every launch, as asked)
+    if (P->sp_wide_mode < 0 && R.gaveup_host && *R.gaveup_host.get() && !P->sp_wide_off) {  // (auto mode only: mode 1 = every launch, as asked)
         P->sp_wide_off = true;
         fprintf(stderr, "[mortal_amd] small-pool SP schedule switched off for this pool: mj_k_sp_wide and mj_k_sp_promo did not run side by side "
-                        "(%llu wide workgroups gave up waiting; more concurrent streams than hardware queues?)\n", *R.gaveup_host);
+                        "(%llu wide workgroups gave up waiting; more concurrent streams than hardware queues?)\n", *R.gaveup_host.get());
     }
     const bool hybrid = R.spare > 0 && !P->sp_wide_off && (P->sp_wide_mode > 0 || (P->sp_wide_mode < 0 && n <= P->sp_wide_max_rows));
     kp.promo_cap = hybrid ? R.spare : 0;
@@ -891,8 +844,9 @@ static int sp_launch(MjPool* P, int agent, float* obs, int n, hipStream_t s) {
     kp.promo_min[2] = P->sp_promo_min[2] > 0 ? P->sp_promo_min[2] : n <= 12000 ? 400 : 1 << 30;
     kp.n_narrow = grid;
     // queue order: rows counting-sorted by cost class, heaviest first (inside the timed mj_k_sp region)
-    hipLaunchKernelGGL(mj_k_order_classify, dim3((n + 255) / 256), dim3(256), 0, s, P->snap, kp.rows, n, R.cls, R.queue + 1);
-    hipLaunchKernelGGL(mj_k_order_scatter, dim3((n + 255) / 256), dim3(256), 0, s, R.cls, n, R.queue + 1, R.queue + 9, R.order);
+    hipLaunchKernelGGL(mj_k_order_classify, dim3((n + 255) / 256), dim3(256), 0, s, P->snap.get(), kp.rows, n, R.cls.get(), R.queue.get() + 1);
+    hipLaunchKernelGGL(mj_k_order_scatter, dim3((n + 255) / 256), dim3(256), 0, s, R.cls.get(), n, R.queue.get() + 1, R.queue.get() + 9,
+                       R.order.get());
     if (!hybrid) {
         hipLaunchKernelGGL(mj_k_sp, dim3(grid), dim3(SP_THREADS), 0, s, kp);
     } else {
@@ -910,19 +864,19 @@ static int sp_launch(MjPool* P, int agent, float* obs, int n, hipStream_t s) {
             }
             hipLaunchKernelGGL(mj_k_sp_promo, dim3(grid), dim3(SP_THREADS), 0, s, kp);
         } else {
-            HIP_OK(hipEventRecord(R.ev_fork, s));
+            HIP_OK(hipEventRecord(R.ev_fork.get(), s));
             hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, kp);
-            HIP_OK(hipStreamWaitEvent(R.stream2, R.ev_fork, 0));
-            hipLaunchKernelGGL(mj_k_sp_promo, dim3(grid), dim3(SP_THREADS), 0, R.stream2, kp);
-            HIP_OK(hipEventRecord(R.ev_join, R.stream2));
-            HIP_OK(hipStreamWaitEvent(s, R.ev_join, 0));
+            HIP_OK(hipStreamWaitEvent(R.stream2.get(), R.ev_fork.get(), 0));
+            hipLaunchKernelGGL(mj_k_sp_promo, dim3(grid), dim3(SP_THREADS), 0, R.stream2.get(), kp);
+            HIP_OK(hipEventRecord(R.ev_join.get(), R.stream2.get()));
+            HIP_OK(hipStreamWaitEvent(s, R.ev_join.get(), 0));
         }
         kp.sweep = 1;
         hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, kp);
-        HIP_OK(hipMemcpyAsync(R.gaveup_host, R.err + SP_ERR_WIDE_GAVEUP, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(R.gaveup_host.get(), R.err.get() + SP_ERR_WIDE_GAVEUP, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     }
 #ifdef SP_ROWDUMP
-    if (kp.rowdump && rowdump_end(P, kp, s)) return -1;
+    if (kp.rowdump && rowdump_end(P, kp, dump, s)) return -1;
 #endif
     return 0;
 }
@@ -933,21 +887,21 @@ int mj_encode(MjPool* P, int agent, float* obs, uint8_t* masks, void* stream) {
     int n = P->last_rows[agent & 1];
     if (n == 0) return 0;
     EncParams ep;
-    ep.blocks = P->blocks;
-    ep.rows = P->rows[agent & 1];
+    ep.blocks = P->blocks.get();
+    ep.rows = P->rows[agent & 1].get();
     ep.n_rows = n;
     ep.tables = g_tables.dev;
     ep.obs = obs;
     ep.masks = masks;
     ep.version = P->version[agent & 1];
     ep.C = mj_obs_rows(ep.version);
-    ep.snap = P->snap;
+    ep.snap = P->snap.get();
     ep.decay_lut = g_tables.decay;
     ep.rbf_score = g_tables.rbf_score;
     ep.rbf_6 = g_tables.rbf_6;
     ep.rbf_12 = g_tables.rbf_12;
     ep.rbf_23 = g_tables.rbf_23;
-    ep.err_flag = P->enc_flag;
+    ep.err_flag = P->enc_flag.get();
     size_t lds = enc_lds_bytes(ep.version, P->knobs.enc_lds_pad);
     hipStream_t s = (hipStream_t)stream;
     if (wait_snapshot(P, s)) return -1;
@@ -988,10 +942,10 @@ int mj_encode_oracle(MjPool* P, int agent, float* out, void* stream) {
     int n = P->last_rows[agent & 1];
     if (n == 0) return 0;
     OracleEncParams ep;
-    ep.rows = P->rows[agent & 1];
+    ep.rows = P->rows[agent & 1].get();
     ep.n_rows = n;
     ep.version = P->version[agent & 1];
-    ep.snap = P->snap;
+    ep.snap = P->snap.get();
     ep.out = out;
     ep.all_yama = P->rp_active ? 1 : 0;
     size_t lds = enc_oracle_lds_bytes(ep.version);
@@ -1022,8 +976,8 @@ int mj_random_policy(MjPool* P, int agent, const uint8_t* masks, uint64_t seed, 
     if (!P->rows_valid) return fail("mj_rows_count must be called first");
     int n = P->last_rows[agent & 1];
     if (n == 0) return 0;
-    hipLaunchKernelGGL(mj_k_random_policy, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, P->blocks,
-                       P->rows[agent & 1], masks, n, seed, cycle, actions);
+    hipLaunchKernelGGL(mj_k_random_policy, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, P->blocks.get(),
+                       P->rows[agent & 1].get(), masks, n, seed, cycle, actions);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -1036,7 +990,7 @@ int mj_greedy_policy(MjPool* P, int agent, const uint8_t* masks, const float* ob
     if (n == 0) return 0;
     const int v = P->version[agent & 1];
     const int d0 = v == 1 ? 923 : v == 2 ? 927 : v == 3 ? 919 : 874;  // first row of the discard block (obs_repr.rs:431-476)
-    hipLaunchKernelGGL(mj_k_greedy_policy, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, P->rows[agent & 1], masks,
+    hipLaunchKernelGGL(mj_k_greedy_policy, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, P->rows[agent & 1].get(), masks,
                        obs, mj_obs_rows(v), d0, n, seed, cycle, actions);
     HIP_OK(hipGetLastError());
     return 0;
@@ -1058,15 +1012,15 @@ int mj_counters(MjPool* P, uint64_t out[8], void* stream) {
     if (!P) return fail("null pool");
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
     unsigned long long tmp[8];
-    HIP_OK(hipMemcpy(tmp, P->counters, sizeof tmp, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(tmp, P->counters.get(), sizeof tmp, hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; i++) out[i] = tmp[i];
     out[5] = P->cycles;
     int f = 0;
-    HIP_OK(hipMemcpy(&f, P->enc_flag, sizeof f, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(&f, P->enc_flag.get(), sizeof f, hipMemcpyDeviceToHost));
     out[6] = (unsigned long long)f;  // (the SP block's overflows are added below)
     if (P->sp.err) {
         unsigned long long e2[SP_ERR_WORDS];
-        HIP_OK(hipMemcpy(e2, P->sp.err, sizeof e2, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(e2, P->sp.err.get(), sizeof e2, hipMemcpyDeviceToHost));
         out[6] += e2[SP_ERR_OVERFLOW];
         out[7] = e2[SP_ERR_ROWS];
         const unsigned long long* pass = e2 + SP_ERR_PASS;  // (seven words: SpCtx::pt[0..6])
@@ -1089,6 +1043,16 @@ void mj_emu_sp_placed(uint64_t out[2]) { out[0] = g_sp_emu_placed[0]; out[1] = g
 void mj_emu_sp_lost_claims(uint64_t out[4]) {
     for (int k = 0; k < 2; k++) out[k] = g_sp_emu_lost[2 + k], out[2 + k] = g_sp_emu_lost[k] - g_sp_emu_lost[2 + k];
 }
+#ifdef MJ_EMU_REGISTRY
+// the emulated runtime's registry (tests/host/emu/hip/hip_runtime.h): live buffers (device and pinned) / events / streams, frees and
+// destroys of something not live, allocations and stream synchronises made since the library was loaded
+void mj_emu_alloc_stats(uint64_t out[6]) {
+    const emu::Registry& r = emu::R();
+    out[0] = r.buffers.size(), out[1] = r.events.size(), out[2] = r.streams.size(), out[3] = r.bad_frees, out[4] = r.allocs, out[5] = r.syncs;
+}
+// the nth allocation / the nth stream synchronise from now on fails, once (<= 0: none does)
+void mj_emu_fail_nth(int alloc, int sync) { emu::R().fail_alloc_in = alloc, emu::R().fail_sync_in = sync; }
+#endif
 #endif
 
 int mj_sp_phase_ticks(MjPool* P, uint64_t out[8], void* stream) {
@@ -1097,7 +1061,7 @@ int mj_sp_phase_ticks(MjPool* P, uint64_t out[8], void* stream) {
     if (!P->sp.err) return 0;  // no obs-v4 encode has run yet
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
     unsigned long long e2[8];  // SP_ERR_OVERFLOW .. SP_ERR_STATES
-    HIP_OK(hipMemcpy(e2, P->sp.err, sizeof e2, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(e2, P->sp.err.get(), sizeof e2, hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; i++) out[i] = e2[i];
     return 0;
 }
@@ -1120,7 +1084,7 @@ int mj_sp_schedule_stats(MjPool* P, uint64_t out[4], void* stream) {
     if (!P->sp.err) return 0;
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
     unsigned long long e2[SP_ERR_WORDS];
-    HIP_OK(hipMemcpy(e2, P->sp.err, sizeof e2, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(e2, P->sp.err.get(), sizeof e2, hipMemcpyDeviceToHost));
     out[0] = P->sp_hybrid_launches;
     out[1] = e2[SP_ERR_PROMOTED];
     out[2] = e2[SP_ERR_SWEPT];
@@ -1131,47 +1095,40 @@ int mj_sp_schedule_stats(MjPool* P, uint64_t out[4], void* stream) {
 int mj_results(MjPool* P, int32_t* scores, uint8_t* done, void* stream) {
     if (!P) return fail("null pool");
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    HIP_OK(hipMemcpy(scores, P->final_scores, (size_t)P->n_games_total * 4 * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(done, P->final_done, (size_t)P->n_games_total, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(scores, P->final_scores.get(), (size_t)P->n_games_total * 4 * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(done, P->final_done.get(), (size_t)P->n_games_total, hipMemcpyDeviceToHost));
     return 0;
 }
 
 // ---------------------------------------------------------------- Stat over event logs (stat.rs:263-441; mj_stat.hip)
 namespace {
-struct StatBuf {  // device memory of one mj_stat_logs / mj_pool_stat call, freed on every return path
-    void* p = nullptr;
-    ~StatBuf() { if (p) hipFree(p); }
-    int from_host(const void* src, size_t bytes, hipStream_t s) {
-        HIP_OK(hipMalloc(&p, std::max(bytes, (size_t)8)));
-        if (bytes) HIP_OK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
-        return 0;
-    }
-};
 // launches mj_k_log_stat with K's inputs, copies the outputs to the host and waits for them
 int stat_run(StatParams K, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
              hipStream_t s) {
     if (!totals_out || !counts_out) return fail("null totals / counts buffer");
     const size_t n = (size_t)K.n_logs, n_out = 2 * MJ_STAT_FIELDS + 3;
-    StatBuf b_seats, b_out, b_per;
+    DevBuf<uint8_t> b_seats;
+    DevBuf<unsigned long long> b_out;
+    DevBuf<long long> b_per;
     if (seats_host) {
-        if (b_seats.from_host(seats_host, n, s)) return -1;
-        K.seats = (const uint8_t*)b_seats.p;
+        if (stat_upload(b_seats, seats_host, n, s)) return -1;
+        K.seats = b_seats.get();
     }
-    HIP_OK(hipMalloc(&b_out.p, n_out * sizeof(int64_t)));
-    HIP_OK(hipMemsetAsync(b_out.p, 0, n_out * sizeof(int64_t), s));
-    K.totals = (unsigned long long*)b_out.p;
+    if (b_out.alloc(n_out)) return -1;
+    HIP_OK(hipMemsetAsync(b_out.get(), 0, n_out * sizeof(int64_t), s));
+    K.totals = b_out.get();
     K.counts = K.totals + 2 * MJ_STAT_FIELDS;
     if (per_seat_out) {
-        HIP_OK(hipMalloc(&b_per.p, n * 4 * MJ_STAT_FIELDS * sizeof(int64_t)));
-        K.per_seat = (long long*)b_per.p;
+        if (b_per.alloc(n * 4 * MJ_STAT_FIELDS)) return -1;
+        K.per_seat = b_per.get();
     }
     const int grid = (int)std::min<size_t>((n + STAT_WAVES - 1) / STAT_WAVES, STAT_GRID_MAX);
     hipLaunchKernelGGL(mj_k_log_stat, dim3(grid), dim3(STAT_THREADS), 0, s, K);
     HIP_OK(hipGetLastError());
     int64_t out[2 * MJ_STAT_FIELDS + 3];
-    HIP_OK(hipMemcpyAsync(out, b_out.p, sizeof out, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(out, b_out.get(), sizeof out, hipMemcpyDeviceToHost, s));
     if (per_seat_out)
-        HIP_OK(hipMemcpyAsync(per_seat_out, b_per.p, n * 4 * MJ_STAT_FIELDS * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(per_seat_out, b_per.get(), n * 4 * MJ_STAT_FIELDS * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     memcpy(totals_out, out, 2 * MJ_STAT_FIELDS * sizeof(int64_t));
     memcpy(counts_out, out + 2 * MJ_STAT_FIELDS, 3 * sizeof(int64_t));
@@ -1191,15 +1148,17 @@ int mj_stat_logs(const uint64_t* words_host, const uint32_t* off_host, int n_log
     const size_t n_words = off_host[n_logs];
     if (n_words && !words_host) return fail("mj_stat_logs: null words");
     hipStream_t s = (hipStream_t)stream;
-    StatBuf b_words, b_off, b_groups;
-    if (b_words.from_host(words_host, n_words * sizeof(uint64_t), s) || b_off.from_host(off_host, ((size_t)n_logs + 1) * sizeof(uint32_t), s)) return -1;
+    DevBuf<uint64_t> b_words;
+    DevBuf<uint32_t> b_off;
+    DevBuf<uint8_t> b_groups;
+    if (stat_upload(b_words, words_host, n_words, s) || stat_upload(b_off, off_host, (size_t)n_logs + 1, s)) return -1;
     StatParams K{};
-    K.words = (const uint64_t*)b_words.p;
-    K.off = (const uint32_t*)b_off.p;
+    K.words = b_words.get();
+    K.off = b_off.get();
     K.n_logs = n_logs;
     if (groups_host) {
-        if (b_groups.from_host(groups_host, (size_t)n_logs, s)) return -1;
-        K.groups = (const uint8_t*)b_groups.p;
+        if (stat_upload(b_groups, groups_host, (size_t)n_logs, s)) return -1;
+        K.groups = b_groups.get();
     }
     return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, s);
 }
@@ -1210,12 +1169,12 @@ int mj_pool_stat(MjPool* P, const uint8_t* seats_host, int64_t* totals_out, int6
     if (!P->log) return fail("mj_pool_stat: the event log is not enabled (mj_pool_enable_log)");
     if (P->refill_stride) return fail("mj_pool_stat: not available in refill mode (a restarted table's log has been rewound)");
     hipStream_t s = (hipStream_t)stream;
-    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap, 0));  // behind the last step, whatever its stream
+    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));  // behind the last step, whatever its stream
     StatParams K{};
-    K.words = P->log;
-    K.len = P->log_len;
+    K.words = P->log.get();
+    K.len = P->log_len.get();
     K.stride = P->log_cap;
-    K.blocks = P->blocks;
+    K.blocks = P->blocks.get();
     K.n_logs = P->n_tables;
     return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, s);
 }
@@ -1229,9 +1188,9 @@ __global__ void mj_k_first_error(const TableBlock* blocks, int n_tables, unsigne
 int mj_pool_first_error(MjPool* P, int* table_out, void* stream) {
     if (!P) return fail("null pool");
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* slot = P->counters + 7;  // spare counter word
+    unsigned long long* slot = P->counters.get() + 7;  // spare counter word
     HIP_OK(hipMemsetAsync(slot, 0xFF, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(mj_k_first_error, dim3((P->n_tables + 255) / 256), dim3(256), 0, s, P->blocks, P->n_tables, slot);
+    hipLaunchKernelGGL(mj_k_first_error, dim3((P->n_tables + 255) / 256), dim3(256), 0, s, P->blocks.get(), P->n_tables, slot);
     HIP_OK(hipGetLastError());
     unsigned long long v = 0;
     HIP_OK(hipMemcpyAsync(&v, slot, sizeof v, hipMemcpyDeviceToHost, s));
@@ -1246,7 +1205,7 @@ int mj_debug_table(MjPool* P, int table, void* out, size_t out_size, void* strea
     if (out_size < sizeof(TableOne)) return fail("buffer too small");
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
     std::vector<uint8_t> blk(sizeof(TableBlock));
-    HIP_OK(hipMemcpy(blk.data(), &P->blocks[table >> 6], sizeof(TableBlock), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(blk.data(), &P->blocks.get()[table >> 6], sizeof(TableBlock), hipMemcpyDeviceToHost));
     auto g = build_gather();
     int lane = table & 63;
     for (auto& e : g) memcpy((char*)out + e.dst_off, blk.data() + e.src_off + (size_t)lane * e.size, e.size);

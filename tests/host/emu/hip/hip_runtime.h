@@ -36,6 +36,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <unordered_set>
 #include <vector>
 
 #define __global__
@@ -465,30 +466,74 @@ template <class P, class T> inline bool emu_cas(P p, T* expected, T desired) {
 #endif
 
 // ---- runtime API (host memory stands in for HBM)
+// Every buffer (device and pinned alike), event and stream is registered while it lives, so a test can count leaks; a free / destroy
+// of something that is not live is counted and SKIPPED (a double free would kill the test process); and the k-th allocation or
+// the k-th stream synchronise (where the real runtime reports what went wrong in the work queued before it) from now on can be
+// made to fail, once (tests/test_emu_alloc_failures.py, through mj_emu_alloc_stats / mj_emu_fail_nth).
+#define MJ_EMU_REGISTRY 1  // (mj_capi.hip exports mj_emu_alloc_stats / mj_emu_fail_nth where the stub has the registry)
+namespace emu {
+struct Registry {
+    std::unordered_set<void*> buffers, events, streams;
+    unsigned long long bad_frees = 0, allocs = 0, syncs = 0;  // hipMalloc + hipHostMalloc / hipStreamSynchronize calls so far
+    long long fail_alloc_in = 0, fail_sync_in = 0;            // > 0: that many such calls from now, the last of them fails
+    static bool due(long long& in) { return in > 0 && --in == 0; }
+};
+inline Registry& R() {
+    static Registry r;
+    return r;
+}
+inline hipError_t release(std::unordered_set<void*>& live, void* p) {
+    if (!live.erase(p)) { R().bad_frees++; return 1; }
+    return 0;
+}
+}  // namespace emu
 inline hipError_t hipMalloc(void** p, size_t n) {
-    *p = n ? aligned_alloc(256, (n + 255) & ~(size_t)255) : nullptr;
-    return (*p || !n) ? 0 : 2;
+    emu::Registry& r = emu::R();
+    *p = nullptr;
+    r.allocs++;
+    if (r.due(r.fail_alloc_in)) return 2;
+    if (!n) return 0;
+    *p = aligned_alloc(256, (n + 255) & ~(size_t)255);
+    if (!*p) return 2;
+    r.buffers.insert(*p);
+    return 0;
 }
 template <class T> inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p, n); }
-inline hipError_t hipFree(void* p) { free(p); return 0; }
+inline hipError_t hipFree(void* p) {
+    if (!p) return 0;
+    if (emu::release(emu::R().buffers, p)) return 1;
+    free(p);
+    return 0;
+}
 template <class T> inline hipError_t hipHostMalloc(T** p, size_t n, unsigned = 0) { return hipMalloc((void**)p, n); }
-inline hipError_t hipHostFree(void* p) { free(p); return 0; }
+inline hipError_t hipHostFree(void* p) { return hipFree(p); }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return 0; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if (n) memcpy(d, s, n); return 0; }
 inline hipError_t hipMemset(void* d, int v, size_t n) { if (n) memset(d, v, n); return 0; }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { if (n) memset(d, v, n); return 0; }
 template <class T> inline hipError_t hipMemcpyToSymbol(T& sym, const void* src, size_t n) { memcpy((void*)&sym, src, n); return 0; }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
+inline hipError_t hipStreamSynchronize(hipStream_t) {
+    emu::R().syncs++;
+    return emu::Registry::due(emu::R().fail_sync_in) ? 3 : 0;
+}
 #define hipStreamNonBlocking 1u
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = nullptr; return 0; }
-inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { emu::R().streams.insert(*s = new char); return 0; }  // (a token: launches ignore the stream)
+inline hipError_t hipStreamDestroy(hipStream_t s) {
+    if (emu::release(emu::R().streams, s)) return 1;
+    delete (char*)s;
+    return 0;
+}
 inline hipError_t hipDeviceSynchronize() { return 0; }
 inline hipError_t hipGetLastError() { return 0; }
 inline const char* hipGetErrorString(hipError_t) { return "emu"; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new EmuEvent{0}; return 0; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { emu::R().events.insert(*e = new EmuEvent{0}); return 0; }
 #define hipEventDisableTiming 2u
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new EmuEvent{0}; return 0; }
-inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return 0; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
+inline hipError_t hipEventDestroy(hipEvent_t e) {
+    if (emu::release(emu::R().events, e)) return 1;
+    delete e;
+    return 0;
+}
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = nullptr) { e->t_ms = emu::now_ms(); return 0; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }  // (the emulator runs every launch to completion)
