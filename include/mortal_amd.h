@@ -25,6 +25,9 @@
  *   mj_results            arena/result.rs:19-30 GameResult.scores; arena/one_vs_three.rs:55-60 ranking input
  *   mj_counters           arena/game.rs:298-311 cycles/actions progress counters
  *   mj_pool_stat, mj_stat_logs   stat.rs:263-441 Stat::from_game, summed as stat.rs:443-498 Stat::from_dir sums the games of a run
+ *   mj_replay_load_pool   arena/result.rs:32-51 dump_json_log -> dataset/gameplay.rs:66-124 load_gz_log_files (the log files between
+ *                         self-play and the loader), without the files: the arena's device log is the loader's script
+ *   mj_pool_grp, mj_grp_logs     dataset/grp.rs:90-164 Grp::load_events
  */
 #ifndef MORTAL_AMD_H
 #define MORTAL_AMD_H
@@ -110,6 +113,17 @@ int mj_step_ev(MjPool* pool, const int32_t* actions_dev0, const int32_t* actions
 int mj_replay_load(MjPool* pool, const uint64_t* script_host, const uint32_t* off_host, const uint8_t* tracked_host,
                    int n_logs, int always_include_kan_select, const uint64_t* nonces_host /* NULL ok */,
                    const uint64_t* keys_host /* NULL ok */);
+/* The same load, from the device log of another pool (arena/result.rs:32-51 dump_json_log + dataset/gameplay.rs:66-124
+ * load_gz_log_files without the files and the JSON between them): log t of `dst` = the log of src's table table0 + t, for all
+ * dst->n_tables tables, copied on the device.  A table whose game has not finished without an error (done != 1) gets an empty
+ * script and is counted as skipped; one whose log_len exceeds the log's capacity or whose event chain runs past its end or meets an
+ * unknown event type is counted as malformed and gets an empty script too.  counts_out = {loaded, skipped, malformed}.
+ * tracked_host: [dst n_tables] seat masks, NULL = all four seats.  deal_from_seed: every start_kyoku asks for the wall to be rebuilt
+ * from the seed (LG_SK_DEAL_BIT) and dst's table t takes the seed of src's table table0 + t.  Needs mj_pool_enable_log on src;
+ * an error if src is in refill mode (a restarted table's log has been rewound), if src == dst or if the range leaves src.  Ordered
+ * behind the steps of src already launched; synchronous; src is never modified.  Afterwards dst is where mj_replay_load leaves it. */
+int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tracked_host /* NULL ok */,
+                        int always_include_kan_select, int deal_from_seed, int64_t counts_out[3], void* stream);
 int mj_replay_step(MjPool* pool, void* stream);
 int mj_replay_meta(MjPool* pool, int32_t* meta_dev, void* stream);
 
@@ -210,6 +224,23 @@ int mj_stat_logs(const uint64_t* words_host, const uint32_t* off_host /* [n_logs
  * launched on `stream`; synchronous.  An error in refill mode: a restarted table's log has been rewound. */
 int mj_pool_stat(MjPool* pool, const uint8_t* seats_host /* [n_tables], NULL = all */, int64_t* totals_out,
                  int64_t* per_seat_out /* NULL or [n_tables][4][MJ_STAT_FIELDS] */, int64_t counts_out[3], void* stream);
+
+/* ---- Grp::load_events (dataset/grp.rs:90-164) reduced from packed event logs on the device (kernel: mortal_amd/csrc/mj_gameplay.hip).
+ * Addressing and host arrays as mj_stat_logs.  Per log: n_kyoku_out = its number of start_kyoku events, feat_out[k] = {grand kyoku
+ * (grp.rs:135-139), honba, kyotaku, scores[4]} of the k-th as raw integers (the reference's f64 feature is score / 10000., left to the
+ * caller: the same f64 division gives the same bits), rank_out = rank_by_player, final_out = final_scores (the last kyoku's scores
+ * plus its deltas, minus 1000 per accepted riichi; ranks stable, ties to the lower seat; what a sum below 100,000 lacks goes to
+ * first place after ranking).  counts_out = {logs reduced, skipped (length 0: n_kyoku 0), malformed (no start_kyoku, more than
+ * max_kyoku of them, an unknown event type or a chain that runs past the end of the log: n_kyoku -1)}; a skipped or malformed
+ * log's other outputs are zeros.  Synchronous. */
+int mj_grp_logs(const uint64_t* words_host, const uint32_t* off_host /* [n_logs + 1] */, int n_logs, int max_kyoku,
+                int32_t* feat_out /* [n_logs][max_kyoku][7] */, int32_t* n_kyoku_out /* [n_logs] */, int32_t* rank_out /* [n_logs][4] */,
+                int32_t* final_out /* [n_logs][4] */, int64_t counts_out[3], void* stream);
+/* The same over tables [table0, table0 + n) of the pool's own device log, in place; tables are skipped as by mj_pool_stat (running, or
+ * in error), a log_len beyond the log's capacity is malformed.  Needs mj_pool_enable_log; an error in refill mode; ordered behind the
+ * steps already launched; synchronous. */
+int mj_pool_grp(MjPool* pool, int table0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
+                int32_t* final_out, int64_t counts_out[3], void* stream);
 
 /* First table in error: returns its error code (>0) and index, or 0. */
 int mj_pool_first_error(MjPool* pool, int* table_out, void* stream);

@@ -346,6 +346,18 @@ class BatchRunner:
         name are summed there too, stat.rs:443-498)."""
         return _stats_by_name([c["name"] for c in self.cfg], [t.counters() for t in self.agent_stats()])
 
+    def gameplays(self, loader, seats=None):
+        """After run(): the training samples of every game, replayed from the device log without a file in between
+        (GameplayLoader.load_pool; keep_log / keep_stat, anything that enabled the device log) -> a list per game of Gameplay,
+        one per wanted seat, named like the dumped logs name the seats (game.rs:186).  seats: 4-bit seat mask per game."""
+        if not getattr(self.pool, "log_cap", 0):
+            raise MortalAmdError("gameplays: the device log is off (create the runner with keep_log or keep_stat)")
+        names_of_agent = [c["name"] for c in self.cfg]
+        if len(names_of_agent) == 1:
+            names_of_agent = names_of_agent * 2
+        names = [[names_of_agent[(int(self.agent_of_seat[g]) >> s) & 1] for s in range(4)] for g in range(self.pool.n_tables)]
+        return loader.load_pool(self.pool, seats=seats, names=names)
+
     @staticmethod
     def _meta(batch, row, tag, with_batch=False):
         """Metadata of one decision (agent/mortal.rs:161-186 gen_meta + :575-591), keys in the order of mjai::Metadata."""

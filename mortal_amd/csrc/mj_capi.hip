@@ -1,5 +1,5 @@
 // C-ABI host side (include/mortal_amd.h): pool life-cycle and kernel launches.  One translation unit for the whole
-// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip.
+// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip / mj_gameplay.hip.
 // Host float math below builds bit-exact LUTs: compile with -ffp-contract=off.
 // Ownership: whatever the host takes from the HIP runtime is held by an owner of mj_host.h and released by its destructor; a call that
 // returns an error leaves the pool as it was before the call (a fallible call builds into locals and moves them in as its last step).
@@ -21,6 +21,7 @@
 #include "mj_encode.hip"
 #include "mj_sp.hip"
 #include "mj_stat.hip"
+#include "mj_gameplay.hip"
 
 static_assert(sizeof(MjAlgoQuery) == 72, "MjAlgoQuery layout");
 // include/mortal_amd.h mj_algo_query: one thread per query, the same device functions the step / encode / SP kernels call
@@ -1177,6 +1178,149 @@ int mj_pool_stat(MjPool* P, const uint8_t* seats_host, int64_t* totals_out, int6
     K.blocks = P->blocks.get();
     K.n_logs = P->n_tables;
     return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, s);
+}
+
+// ---------------------------------------------------------------- samples and Grp from packed logs (mj_gameplay.hip)
+namespace {
+// grid of the wavefront-per-log kernels; MJ_LOG_GRID caps it (tests: few workgroups, many logs each)
+int log_grid(size_t n_logs) {
+    int grid = (int)std::min<size_t>((n_logs + LOGK_WAVES - 1) / LOGK_WAVES, LOGK_GRID_MAX);
+    if (const char* v = getenv("MJ_LOG_GRID")) grid = std::min(grid, atoi(v));
+    return std::max(grid, 1);
+}
+LogSrc pool_log_src(const MjPool* P, int table0, int n) {
+    LogSrc S{};
+    S.words = P->log.get();
+    S.len = P->log_len.get();
+    S.stride = P->log_cap;
+    S.blocks = P->blocks.get();
+    S.table0 = table0;
+    S.n_logs = n;
+    return S;
+}
+// launches mj_k_log_grp over S, copies the outputs to the host and waits for them
+int grp_run(const LogSrc& S, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out, int32_t* final_out,
+            int64_t counts_out[3], hipStream_t s) {
+    const size_t n = (size_t)S.n_logs, n_feat = n * (size_t)max_kyoku * 7;
+    DevBuf<int32_t> b_feat, b_small;  // b_small: n_kyoku [n], rank [n][4], final [n][4]
+    DevBuf<unsigned long long> b_counts;
+    if (b_feat.alloc(n_feat) || b_small.alloc(n * 9) || b_counts.alloc(3)) return -1;
+    HIP_OK(hipMemsetAsync(b_feat.get(), 0, n_feat * sizeof(int32_t), s));
+    HIP_OK(hipMemsetAsync(b_counts.get(), 0, 3 * sizeof(unsigned long long), s));
+    const GrpParams K = {S, max_kyoku, b_feat.get(), b_small.get(), b_small.get() + n, b_small.get() + n * 5, b_counts.get()};
+    hipLaunchKernelGGL(mj_k_log_grp, dim3(log_grid(n)), dim3(LOGK_THREADS), 0, s, K);
+    HIP_OK(hipGetLastError());
+    int64_t counts[3];
+    HIP_OK(hipMemcpyAsync(feat_out, K.feat, n_feat * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(n_kyoku_out, K.n_kyoku, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(rank_out, K.rank, n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(final_out, K.final_, n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(counts, K.counts, sizeof counts, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    memcpy(counts_out, counts, sizeof counts);
+    return 0;
+}
+int grp_args(const char* who, int n, int max_kyoku, const void* feat, const void* n_kyoku, const void* rank, const void* final_,
+             int64_t* counts_out) {
+    if (!counts_out) return fail(std::string(who) + ": null counts buffer");
+    memset(counts_out, 0, 3 * sizeof(int64_t));
+    if (n < 0) return fail(std::string(who) + ": negative number of logs");
+    if (max_kyoku < 1) return fail(std::string(who) + ": max_kyoku must be at least 1");
+    if (n && (!feat || !n_kyoku || !rank || !final_)) return fail(std::string(who) + ": null output buffer");
+    return 0;
+}
+}  // namespace
+
+int mj_grp_logs(const uint64_t* words_host, const uint32_t* off_host, int n_logs, int max_kyoku, int32_t* feat_out,
+                int32_t* n_kyoku_out, int32_t* rank_out, int32_t* final_out, int64_t counts_out[3], void* stream) {
+    if (grp_args("mj_grp_logs", n_logs, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out)) return -1;
+    if (n_logs == 0) return 0;
+    if (!off_host) return fail("mj_grp_logs: null offsets");
+    for (int i = 0; i < n_logs; i++)  // the kernel trusts the offsets: a log lies inside [0, off[n_logs])
+        if (off_host[i] > off_host[i + 1]) return fail("mj_grp_logs: offsets of log " + std::to_string(i) + " decrease");
+    const size_t n_words = off_host[n_logs];
+    if (n_words && !words_host) return fail("mj_grp_logs: null words");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf<uint64_t> b_words;
+    DevBuf<uint32_t> b_off;
+    if (stat_upload(b_words, words_host, n_words, s) || stat_upload(b_off, off_host, (size_t)n_logs + 1, s)) return -1;
+    LogSrc S{};
+    S.words = b_words.get();
+    S.off = b_off.get();
+    S.n_logs = n_logs;
+    return grp_run(S, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out, s);
+}
+
+int mj_pool_grp(MjPool* P, int table0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
+                int32_t* final_out, int64_t counts_out[3], void* stream) {
+    if (!P) return fail("null pool");
+    if (grp_args("mj_pool_grp", n, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out)) return -1;
+    if (!P->log) return fail("mj_pool_grp: the event log is not enabled (mj_pool_enable_log)");
+    if (P->refill_stride) return fail("mj_pool_grp: not available in refill mode (a restarted table's log has been rewound)");
+    if (table0 < 0 || table0 > P->n_tables - n) return fail("mj_pool_grp: table range out of bounds");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));  // behind the last step, whatever its stream
+    return grp_run(pool_log_src(P, table0, n), max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out, s);
+}
+
+int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tracked_host, int always_include_kan_select,
+                        int deal_from_seed, int64_t counts_out[3], void* stream) {
+    if (!dst || !src) return fail("null pool");
+    if (!counts_out) return fail("mj_replay_load_pool: null counts buffer");
+    memset(counts_out, 0, 3 * sizeof(int64_t));
+    if (src == dst) return fail("mj_replay_load_pool: the source pool cannot be its own destination (the load restarts the destination's tables)");
+    if (!src->log) return fail("mj_replay_load_pool: the event log of the source pool is not enabled (mj_pool_enable_log)");
+    if (src->refill_stride) return fail("mj_replay_load_pool: not available in refill mode (a restarted table's log has been rewound)");
+    const int n = dst->n_tables;
+    if (table0 < 0 || table0 > src->n_tables - n) return fail("mj_replay_load_pool: table range out of bounds");
+    hipStream_t s = (hipStream_t)stream;
+    // everything is built beside the destination and moved in last: its tables and counters too, so that no failure -- the last
+    // synchronise included -- can leave it between two scripts
+    ReplayBufs R;
+    DevBuf<TableBlock> blocks;
+    DevBuf<unsigned long long> counters, sums;  // sums: loaded / skipped / malformed, total words
+    DevBuf<uint32_t> len;
+    if (R.off.alloc((size_t)n + 1) || R.cursor.alloc(n) || R.ev_index.alloc(n) || R.kyoku.alloc(n) || R.tracked.alloc(n) ||
+        R.label.alloc((size_t)n * 4) || R.kan_label.alloc((size_t)n * 4) || blocks.alloc(dst->n_blocks) || counters.alloc(8) ||
+        sums.alloc(4) || len.alloc(n))
+        return -1;
+    if (tracked_host) HIP_OK(hipMemcpyAsync(R.tracked.get(), tracked_host, (size_t)n, hipMemcpyHostToDevice, s));
+    else HIP_OK(hipMemsetAsync(R.tracked.get(), 0x0F, (size_t)n, s));
+    HIP_OK(hipMemsetAsync(R.cursor.get(), 0, (size_t)n * sizeof(uint32_t), s));
+    HIP_OK(hipMemsetAsync(R.ev_index.get(), 0, (size_t)n * sizeof(uint32_t), s));
+    HIP_OK(hipMemsetAsync(R.kyoku.get(), 0, (size_t)n, s));
+    HIP_OK(hipMemsetAsync(blocks.get(), 0, (size_t)dst->n_blocks * sizeof(TableBlock), s));
+    HIP_OK(hipMemsetAsync(counters.get(), 0, 8 * sizeof(unsigned long long), s));
+    HIP_OK(hipMemsetAsync(sums.get(), 0, 4 * sizeof(unsigned long long), s));
+    R.always_kan = always_include_kan_select;
+    if (src->ev_snap && s != src->step_stream) HIP_OK(hipStreamWaitEvent(s, src->ev_snap.get(), 0));  // behind the source's last step
+    const LogSrc S = pool_log_src(src, table0, n);
+    const int grid = log_grid((size_t)n);
+    const LogLenParams lp = {S, len.get(), sums.get()};
+    hipLaunchKernelGGL(mj_k_log_len, dim3(grid), dim3(LOGK_THREADS), 0, s, lp);
+    hipLaunchKernelGGL(mj_k_log_scan, dim3(1), dim3(1024), 0, s, len.get(), n, R.off.get(), sums.get() + 3);
+    const TableBlock* seeds_of = deal_from_seed ? src->blocks.get() : nullptr;
+    hipLaunchKernelGGL(mj_k_log_fresh, dim3(dst->n_blocks), dim3(64), 0, s, blocks.get(), n, seeds_of, table0);
+    HIP_OK(hipGetLastError());
+    unsigned long long sums_host[4];
+    HIP_OK(hipMemcpyAsync(sums_host, sums.get(), sizeof sums_host, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (sums_host[3] > 0xFFFFFFFFull)
+        return fail("mj_replay_load_pool: " + std::to_string(sums_host[3]) + " script words do not fit the 32-bit offsets: load fewer tables per call");
+    if (R.script.alloc((size_t)sums_host[3] + 1)) return -1;
+    const LogPackParams pp = {S, R.off.get(), R.script.get(), deal_from_seed};
+    hipLaunchKernelGGL(mj_k_log_pack, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
+    for (int k = 0; k < 3; k++) counts_out[k] = (int64_t)sums_host[k];
+    dst->blocks = std::move(blocks);  // (what the destination held goes with the locals)
+    dst->counters = std::move(counters);
+    dst->rp = std::move(R);
+    dst->rp_active = true;
+    dst->cycles = 0;
+    dst->rows_valid = false;
+    return 0;
 }
 
 __global__ void mj_k_first_error(const TableBlock* blocks, int n_tables, unsigned long long* out) {

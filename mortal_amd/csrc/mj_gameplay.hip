@@ -1,0 +1,262 @@
+// Training samples from packed event logs without a host codec (the reference's route: arena/result.rs:32-51 dump_json_log ->
+// dataset/gameplay.rs:66-124 load_gz_log_files): a pool's device log becomes the replay script of another pool (mj_k_log_len,
+// mj_k_log_scan, mj_k_log_pack, mj_k_log_fresh), and dataset/grp.rs:90-164 Grp::load_events is reduced from the same words
+// (mj_k_log_grp).
+//
+// Shape, as mj_k_log_stat (mj_stat.hip): one wavefront handles one log at a time, grid-stride over the logs; the 64 lanes load 64
+// consecutive words as one coalesced 512-byte read and the chain of events is followed with wave-uniform __shfl reads of those
+// registers -- no lane streams a log of its own.  An event's length is a function of its header word alone (mj_replay.hip rp_len),
+// so the length pass and the copy walk fixed windows [64 j, 64 j + 64) and carry the chain position across them; the copy stores
+// each window as it was loaded (coalesced), with LG_SK_DEAL_BIT set on the lanes the walk found to hold a start_kyoku header (a
+// payload word can look like one: the headers are known only by walking).  Grp reads payload words (scores, deltas), so
+// mj_k_log_grp restarts its window at an event whose first two payload words could lie outside it, like mj_k_log_stat.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mj_algo.h"
+#include "mj_stat.hip"
+
+#define LOGK_WAVES 4                 // wavefronts (= logs in flight) per workgroup
+#define LOGK_THREADS (64 * LOGK_WAVES)
+#define LOGK_GRID_MAX (256 * 4)      // bounded grid, the rest by grid stride (MJ_LOG_GRID lowers it: tests)
+#define LOGK_WINDOW_LAST 60          // mj_k_log_grp: header + tag + two payload words <= window index 63
+
+// The two addressings of StatParams: concatenated logs with `off`, or tables [table0, table0 + n_logs) of a pool's strided log.
+struct LogSrc {
+    const uint64_t* words;
+    const uint32_t* off;         // [n_logs + 1], or NULL: log i is table table0 + i, at words + table * stride ...
+    const uint32_t* len;         // ... with len[table] words; more than stride = the log overflowed: malformed
+    uint32_t stride;
+    const TableBlock* blocks;    // pool path: flags / err of the table
+    int table0;
+    int n_logs;
+};
+enum { LOG_OK = 0, LOG_SKIP = 1, LOG_BAD = 2 };
+
+// log i -> its words and length; LOG_SKIP: nothing to read (an empty log; a table whose game has not finished without an error,
+// tested as mj_k_log_stat tests it), LOG_BAD: log_len beyond log_cap
+MJD int log_locate(const LogSrc& S, int i, const uint64_t*& lw, uint32_t& len) {
+    if (S.off) {
+        lw = S.words + (size_t)S.off[i];
+        len = S.off[i + 1] - S.off[i];
+        return len ? LOG_OK : LOG_SKIP;
+    }
+    const int t = S.table0 + i;
+    lw = S.words + (size_t)t * S.stride;
+    len = S.len[t];
+    const TableBlock* B = S.blocks + (t >> 6);
+    const uint32_t fl = B->flags[t & 63];
+    if (!(fl & TF_DONE) || (fl & TF_INACTIVE) || B->err[t & 63] != MJ_OK || len == 0) return LOG_SKIP;
+    return len > S.stride ? LOG_BAD : LOG_OK;
+}
+
+MJD int log_event_len(uint32_t w_lo, uint32_t w_hi) {  // mj_replay.hip rp_len
+    const int t = w_lo & 15;
+    if (t == LG_START_KYOKU) return (w_hi >> (LG_SK_WALL_BIT - 32)) & 1 ? 27 : 10;
+    return (t == LG_HORA ? 4 : t == LG_RYUKYOKU ? 3 : 1) + (int)((w_hi >> (LG_TAG_BIT - 32)) & 1);
+}
+
+// Walks the chain of one log in fixed 64-word windows.  `store`: NULL, or where the words go; `deal_bit`: set LG_SK_DEAL_BIT in
+// every start_kyoku header on the way.  -> the chain is a sequence of known events that ends exactly at `len`.
+MJD bool log_walk(const uint64_t* lw, uint32_t len, int lane, uint64_t* store, bool deal_bit) {
+    uint32_t pos = 0;  // wave-uniform: the next header
+    bool bad = false;
+    for (uint32_t base = 0; base < len; base += 64) {
+        const uint64_t mine = base + (uint32_t)lane < len ? lw[base + lane] : 0ull;  // never beyond len
+        const uint32_t end = min(base + 64u, len);
+        uint64_t sk = 0;  // window lanes that hold a start_kyoku header
+        while (pos < end && !bad) {
+            const int k = __builtin_amdgcn_readfirstlane((int)(pos - base));
+            const uint64_t wv = __shfl(mine, k);
+            const uint32_t w_lo = __builtin_amdgcn_readfirstlane((uint32_t)wv);
+            const uint32_t w_hi = __builtin_amdgcn_readfirstlane((uint32_t)(wv >> 32));
+            const int t = w_lo & 15;
+            if (t < LG_START_KYOKU || t > LG_END_KYOKU) bad = true;
+            if (t == LG_START_KYOKU) sk |= 1ull << k;
+            pos += (uint32_t)log_event_len(w_lo, w_hi);
+        }
+        if (store && base + (uint32_t)lane < len)
+            store[base + lane] = mine | (deal_bit && ((sk >> lane) & 1) ? 1ull << LG_SK_DEAL_BIT : 0ull);
+        if (bad && !store) break;
+    }
+    return !bad && pos == len;
+}
+
+// ---- pass 1: per log the number of words its script takes (0: skipped or malformed), and the three counts
+struct LogLenParams {
+    LogSrc src;
+    uint32_t* len_out;           // [n_logs]
+    unsigned long long* counts;  // [3] loaded / skipped / malformed, added to
+};
+__global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_len(LogLenParams P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned n_ok = 0, n_skip = 0, n_bad = 0;
+    for (int i = blockIdx.x * LOGK_WAVES + wave; i < P.src.n_logs; i += gridDim.x * LOGK_WAVES) {
+        const uint64_t* lw;
+        uint32_t len;
+        int st = log_locate(P.src, i, lw, len);
+        if (st == LOG_OK && !log_walk(lw, len, lane, nullptr, false)) st = LOG_BAD;
+        if (lane == 0) P.len_out[i] = st == LOG_OK ? len : 0u;
+        n_ok += st == LOG_OK, n_skip += st == LOG_SKIP, n_bad += st == LOG_BAD;
+    }
+    const unsigned n_mine = lane == 0 ? n_ok : lane == 1 ? n_skip : n_bad;  // one count per lane
+    if (lane < 3 && n_mine) atomicAdd(&P.counts[lane], (unsigned long long)n_mine);
+}
+
+// ---- pass 2: exclusive scan of the lengths, one workgroup; off[n] = the total's low word, *total = the total
+__global__ __launch_bounds__(1024) void mj_k_log_scan(const uint32_t* len, int n, uint32_t* off, unsigned long long* total) {
+    __shared__ unsigned long long s_wave[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long carry = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + tid;
+        const unsigned long long v = i < n ? len[i] : 0u;
+        unsigned long long x = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) s_wave[wave] = x;
+        __syncthreads();
+        unsigned long long before = 0, tile = 0;
+        for (int w = 0; w < 16; w++) {
+            if (w < wave) before += s_wave[w];
+            tile += s_wave[w];
+        }
+        if (i < n) off[i] = (uint32_t)(carry + before + x - v);
+        carry += tile;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        off[n] = (uint32_t)carry;
+        *total = carry;
+    }
+}
+
+// ---- pass 3: the copy.  Log i goes to script[off[i] .. off[i + 1]) (an empty range for a skipped or malformed one).
+struct LogPackParams {
+    LogSrc src;
+    const uint32_t* off;  // [n_logs + 1]
+    uint64_t* script;
+    int deal_from_seed;
+};
+__global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_pack(LogPackParams P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = blockIdx.x * LOGK_WAVES + wave; i < P.src.n_logs; i += gridDim.x * LOGK_WAVES) {
+        const uint32_t n = P.off[i + 1] - P.off[i];
+        if (n == 0) continue;
+        const uint64_t* lw;
+        uint32_t len;
+        log_locate(P.src, i, lw, len);  // (n == len: pass 1 accepted this log)
+        uint64_t* out = P.script + (size_t)P.off[i];
+        if (P.deal_from_seed) {
+            log_walk(lw, n, lane, out, true);
+        } else {
+            for (uint32_t k = lane; k < n; k += 64) out[k] = lw[k];
+        }
+    }
+}
+
+// ---- the destination's tables at the start of a replay (mj_capi.hip fresh_blocks, on the device): `fresh` arrives zeroed; the
+// padding lanes of the last block are inactive; with `src`, table i takes the seed of the source's table table0 + i
+__global__ __launch_bounds__(64) void mj_k_log_fresh(TableBlock* fresh, int n_tables, const TableBlock* src, int table0) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    TableBlock* B = fresh + blockIdx.x;
+    const int l = threadIdx.x;
+    if (i >= n_tables) {
+        B->flags[l] = TF_INACTIVE | TF_DONE | TF_ENDED;
+    } else if (src) {
+        const int t = table0 + i;
+        B->seed_nonce[l] = src[t >> 6].seed_nonce[t & 63];
+        B->seed_key[l] = src[t >> 6].seed_key[t & 63];
+    }
+}
+
+// ---- Grp::load_events (dataset/grp.rs:90-164), forwards: a start_kyoku records its row and restarts the running scores, hora /
+// ryukyoku add their deltas, reach_accepted takes 1000; what stands at the end is what the reference's reverse walk collects up
+// to the last start_kyoku.
+struct GrpParams {
+    LogSrc src;
+    int max_kyoku;
+    int32_t* feat;      // [n_logs][max_kyoku][7] raw: grand kyoku, honba, kyotaku, scores[4]; zeroed by the caller
+    int32_t* n_kyoku;   // [n_logs]: rows written; 0 for a skipped log, -1 for a malformed one
+    int32_t* rank;      // [n_logs][4] rank_by_player
+    int32_t* final_;    // [n_logs][4] final_scores
+    unsigned long long* counts;  // [3] reduced / skipped / malformed, added to
+};
+__global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_grp(GrpParams P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pid = lane & 3;
+    unsigned n_ok = 0, n_skip = 0, n_bad = 0;
+    for (int log = blockIdx.x * LOGK_WAVES + wave; log < P.src.n_logs; log += gridDim.x * LOGK_WAVES) {
+        const uint64_t* lw;
+        uint32_t len;
+        int st = log_locate(P.src, log, lw, len);
+        int32_t* const F = P.feat + (size_t)log * P.max_kyoku * 7;
+        int nk = 0, cur0 = 0, cur1 = 0, cur2 = 0, cur3 = 0;  // wave-uniform
+        if (st == LOG_OK) {
+            bool bad = false;
+            uint32_t pos = 0;
+            while (pos < len && !bad) {
+                const uint32_t base = pos;
+                const uint64_t mine = base + (uint32_t)lane < len ? lw[base + lane] : 0ull;  // never beyond len
+                while (pos < len && pos - base <= LOGK_WINDOW_LAST) {
+                    const int k = __builtin_amdgcn_readfirstlane((int)(pos - base));
+                    const uint64_t wv = __shfl(mine, k);
+                    const uint32_t w_lo = __builtin_amdgcn_readfirstlane((uint32_t)wv);
+                    const uint32_t w_hi = __builtin_amdgcn_readfirstlane((uint32_t)(wv >> 32));
+                    const int t = w_lo & 15, actor = (w_lo >> 4) & 3;
+                    if (t < LG_START_KYOKU || t > LG_END_KYOKU) { bad = true; break; }
+                    const uint32_t next = pos + (uint32_t)log_event_len(w_lo, w_hi);
+                    if (next > len) { bad = true; break; }  // the chain runs past the end of the log
+                    pos = next;
+                    if (t != LG_START_KYOKU && t != LG_HORA && t != LG_RYUKYOKU) {
+                        if (t == LG_REACH_ACCEPTED) {
+                            cur0 -= actor == 0 ? 1000 : 0, cur1 -= actor == 1 ? 1000 : 0;
+                            cur2 -= actor == 2 ? 1000 : 0, cur3 -= actor == 3 ? 1000 : 0;
+                        }
+                        continue;
+                    }
+                    const int p = k + 1 + (t != LG_START_KYOKU ? (int)((w_hi >> (LG_TAG_BIT - 32)) & 1) : 0);  // first payload word
+                    const uint64_t a = __shfl(mine, p), b = __shfl(mine, p + 1);
+                    const int d0 = (int)(uint32_t)a, d1 = (int)(uint32_t)(a >> 32), d2 = (int)(uint32_t)b, d3 = (int)(uint32_t)(b >> 32);
+                    if (t != LG_START_KYOKU) {
+                        cur0 += d0, cur1 += d1, cur2 += d2, cur3 += d3;
+                        continue;
+                    }
+                    if (nk >= P.max_kyoku) { bad = true; break; }
+                    const int c0 = (w_lo >> 14) & 63;  // bakaze * 4 + kyoku - 1; grp.rs:135-139 counts west and north alike
+                    const int grand = c0 < 12 ? c0 : c0 - 4;
+                    const int honba = (w_hi >> (LG_HONBA_SHIFT - 32)) & 0xFF, kyotaku = (w_hi >> (LG_KYOTAKU_SHIFT - 32)) & 0xFF;
+                    if (lane < 7)
+                        F[nk * 7 + lane] = lane == 0 ? grand : lane == 1 ? honba : lane == 2 ? kyotaku : stat_pick(lane - 3, d0, d1, d2, d3);
+                    nk++;
+                    cur0 = d0, cur1 = d1, cur2 = d2, cur3 = d3;
+                }
+            }
+            if (bad || nk == 0) {
+                st = LOG_BAD;
+                for (int r = 0; r < nk; r++)  // (the lanes that wrote the rows take them back)
+                    if (lane < 7) F[r * 7 + lane] = 0;
+            }
+        }
+        if (lane < 4) {
+            int rank = 0, final_score = 0;
+            if (st == LOG_OK) {
+                // Rankings::new: stable, ties to the lower seat; the top-up to 100,000 goes to first place after ranking
+                const int mine_c = stat_pick(pid, cur0, cur1, cur2, cur3);
+                rank = (cur0 > mine_c || (cur0 == mine_c && 0 < pid)) + (cur1 > mine_c || (cur1 == mine_c && 1 < pid)) +
+                       (cur2 > mine_c || (cur2 == mine_c && 2 < pid)) + (cur3 > mine_c || (cur3 == mine_c && 3 < pid));
+                const int total = cur0 + cur1 + cur2 + cur3;
+                final_score = mine_c + (rank == 0 && total < 100000 ? 100000 - total : 0);
+            }
+            P.rank[(size_t)log * 4 + lane] = rank;
+            P.final_[(size_t)log * 4 + lane] = final_score;
+        }
+        if (lane == 0) P.n_kyoku[log] = st == LOG_OK ? nk : st == LOG_SKIP ? 0 : -1;
+        n_ok += st == LOG_OK, n_skip += st == LOG_SKIP, n_bad += st == LOG_BAD;
+    }
+    const unsigned n_mine = lane == 0 ? n_ok : lane == 1 ? n_skip : n_bad;  // one count per lane
+    if (lane < 3 && n_mine) atomicAdd(&P.counts[lane], (unsigned long long)n_mine);
+}

@@ -77,6 +77,17 @@ class Grp:
         return Grp(np.array(game_info, dtype=np.float64).reshape(len(game_info), GRP_SIZE), rank_by_player, final_scores)
 
     @staticmethod
+    def from_packed(words_list, max_kyoku=64, lib=None):
+        """The same from packed event words (mjai_log.encode_events, TablePool.read_logs), every log of the list reduced on the
+        device (mj_grp_logs) -> list of Grp.  ValueError for a log load_events would refuse (no start_kyoku), a malformed one
+        or one of more than max_kyoku kyoku."""
+        grps, _n_kyoku, _counts = grp_logs(words_list, max_kyoku, lib)
+        for i, g in enumerate(grps):
+            if g is None:
+                raise ValueError(f"log {i}: invalid log (empty, malformed, no StartKyoku or more than {max_kyoku} kyoku)")
+        return grps
+
+    @staticmethod
     def load_log(raw_log):
         return Grp.load_events(_parse(raw_log))
 
@@ -102,6 +113,55 @@ class Grp:
 
     def take_final_scores(self):
         return list(self.final_scores)
+
+
+def _grp_call(call, n_logs, max_kyoku):
+    """Shared by grp_logs and TablePool.log_grp: allocate the outputs, run `call(feat ptr, n_kyoku ptr, rank ptr, final ptr,
+    counts ptr)`, wrap the result -> (list of Grp or None per log, n_kyoku int32 [n], counts dict)."""
+    feat = np.zeros((n_logs, max_kyoku, GRP_SIZE), dtype=np.int32)
+    n_kyoku = np.zeros(n_logs, dtype=np.int32)
+    rank = np.zeros((n_logs, 4), dtype=np.int32)
+    final = np.zeros((n_logs, 4), dtype=np.int32)
+    counts = np.zeros(3, dtype=np.int64)
+    call(feat.ctypes.data, n_kyoku.ctypes.data, rank.ctypes.data, final.ctypes.data, counts.ctypes.data)
+    grps = []
+    for i in range(n_logs):
+        k = int(n_kyoku[i])
+        if k <= 0:
+            grps.append(None)
+            continue
+        f = feat[i, :k].astype(np.float64)
+        f[:, 3:] = feat[i, :k, 3:].astype(np.float64) / 10000.0  # grp.rs:144 `score as f64 / 10000.`
+        grps.append(Grp(f, [int(x) for x in rank[i]], [int(x) for x in final[i]]))
+    return grps, n_kyoku, dict(reduced=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2]))
+
+
+def grp_logs(words_list, max_kyoku=64, lib=None):
+    """`Grp.load_events` of every log on the device, from packed event words (mjai_log.encode_events, TablePool.read_logs;
+    mj_grp_logs).  -> (list of Grp, None for an empty or malformed log; n_kyoku int32 [n]: 0 for an empty log, -1 for a malformed
+    one -- no start_kyoku, more than max_kyoku of them, an unknown event or a chain that runs past the end; counts
+    dict(reduced, skipped, malformed)).  `lib` is for the test suite (the host emulation of the same sources)."""
+    import ctypes
+
+    n = len(words_list)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in words_list])
+    if int(off[-1]) >= 1 << 32:
+        raise ValueError("grp_logs: more than 2^32 words in one call")
+    off = off.astype(np.uint32)
+    words = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64) for x in words_list]) if n else np.zeros(0),
+                                 dtype=np.uint64)
+    stream = None
+    if lib is None:
+        from ._lib import lib
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call(*ptrs):
+        if lib.mj_grp_logs(words.ctypes.data, off.ctypes.data, n, int(max_kyoku), *ptrs, stream) < 0:
+            from ._lib import MortalAmdError
+            raise MortalAmdError(lib.mj_last_error().decode())
+
+    return _grp_call(call, n, int(max_kyoku))
 
 
 class Gameplay:
@@ -321,43 +381,96 @@ class GameplayLoader:
         pool = self.pool_cls(n, version=self.version, device=self.device, max_rows=8 * n + 64, deal_algo=self.deal_algo)
         try:
             pool.replay_load(scripts, tracked, self.always_include_kan_select, nonces, keys)
-            obs_parts, mask_parts, meta_parts, inv_parts = [], [], [], []
-            for _ in range(total_events + 8):
-                k = pool.replay_step()
-                if k == 0:
-                    if pool.counters()["games"] >= n:
-                        break
-                    continue
-                obs, masks = pool.encode(0)
-                obs_parts.append(obs)
-                mask_parts.append(masks)
-                meta_parts.append(pool.replay_meta())
-                if self.oracle:
-                    inv_parts.append(pool.encode_oracle(0))
-            else:
-                raise RuntimeError("log replay did not terminate")
-            code, tbl = pool.first_error()
-            if code:
-                raise ValueError(f"log {tbl}: the event stream is not a legal game (error code {code})")
-            if pool.counters()["sp_overflow"]:
-                raise RuntimeError("obs v4: a sample's single-player state graph exceeded the device scratch capacity")
+            samples = self._replay_samples(pool, n, total_events + 8)
         finally:
             pool.close()
-        C = OBS_ROWS[self.version]
+        return self._slice_gameplays(games, *samples)
+
+    def load_pool(self, pool, table0=0, n_tables=None, seats=None, names=None):
+        """The samples of a pool's finished games straight from its device log (TablePool.enable_log), without JSON or files:
+        tables [table0, table0 + n_tables) (None = to the last) are replayed on the device from the packed words the arena wrote
+        (mj_replay_load_pool), and their Grp is reduced from the same words (mj_pool_grp).  Returns what load_logs returns for the
+        same games: a list per table of Gameplay, one per wanted seat; the list of a table that is still playing or ended in
+        error is empty.
+
+        seats: 4-bit seat mask per table (None = all four seats); names: four player names per table (None = ""), filtered by
+        player_names / excludes like the names of a log file when given.  oracle=True rebuilds every wall from the table's
+        seed -- logs of this engine always come with their seed, trust_seed does not matter here.  augmented=True is refused:
+        the arena's log is not suit-swapped, and this route has no host encoder that could swap it.
+
+        Memory: all obs of the range are materialised on the device at once (137 KB per obs-v4 sample, about 600 samples per
+        game and seat), so the caller bounds memory by the table range it asks for."""
+        if self.augmented:
+            raise ValueError("load_pool: augmented=True is not supported (the arena's device log is not suit-swapped and this "
+                             "route has no host encoder to swap it): dump the logs and use load_logs / load_gz_log_files")
+        n = pool.n_tables - table0 if n_tables is None else int(n_tables)
+        if table0 < 0 or n < 0 or table0 + n > pool.n_tables:
+            raise ValueError(f"load_pool: tables [{table0}, {table0 + n}) are not in a pool of {pool.n_tables}")
+        if n == 0:
+            return []
+        masks = np.full(n, 15, dtype=np.uint8) if seats is None else np.ascontiguousarray(seats, dtype=np.uint8)
+        if masks.shape != (n,):
+            raise ValueError(f"seats: expected {n} masks, got shape {masks.shape}")
+        if names is not None and len(names) != n:
+            raise ValueError(f"names: expected {n} lists of four names, got {len(names)}")
+        grps = pool.log_grp(table0, n)
+        games = []
+        for t in range(n):
+            nm = list(names[t]) if names is not None else ["", "", "", ""]
+            wanted = [p for p in (self._wanted(nm) if names is not None else range(4)) if (int(masks[t]) >> p) & 1]
+            games.append(dict(names=nm, wanted=wanted if grps[t] is not None else [], grp=grps[t]))
+        tracked = [sum(1 << p for p in g["wanted"]) for g in games]
+        rp = type(pool)(n, version=self.version, device=str(pool.device), max_rows=8 * n + 64, deal_algo=pool.deal_algo)
+        try:
+            rp.replay_load_pool(pool, table0, tracked, self.always_include_kan_select, deal_from_seed=self.oracle)
+            # every step applies at least one event of every unfinished log, and an event takes at least one word
+            samples = self._replay_samples(rp, n, pool.log_cap + 8, table0)
+        finally:
+            rp.close()
+        return self._slice_gameplays(games, *samples)
+
+    def _replay_samples(self, pool, n, max_steps, table0=0):
+        """The replay loop over a loaded pool -> (obs, masks, meta, invisible obs or None), every sample of every tracked seat in
+        the order the device produced them."""
+        obs_parts, mask_parts, meta_parts, inv_parts = [], [], [], []
+        for _ in range(max_steps):
+            k = pool.replay_step()
+            if k == 0:
+                if pool.counters()["games"] >= n:
+                    break
+                continue
+            obs, masks = pool.encode(0)
+            obs_parts.append(obs)
+            mask_parts.append(masks)
+            meta_parts.append(pool.replay_meta())
+            if self.oracle:
+                inv_parts.append(pool.encode_oracle(0))
+        else:
+            raise RuntimeError("log replay did not terminate")
+        code, tbl = pool.first_error()
+        if code:
+            raise ValueError(f"log {table0 + tbl}: the event stream is not a legal game (error code {code})")
+        if pool.counters()["sp_overflow"]:
+            raise RuntimeError("obs v4: a sample's single-player state graph exceeded the device scratch capacity")
         if obs_parts:
             obs = torch.cat(obs_parts)
             masks = torch.cat(mask_parts)
             meta = torch.cat(meta_parts).cpu().numpy()
         else:
-            obs = torch.empty((0, C, 34), dtype=torch.float32, device=self.device)
-            masks = torch.empty((0, ACTION_SPACE), dtype=torch.bool, device=self.device)
+            obs = torch.empty((0, OBS_ROWS[self.version], 34), dtype=torch.float32, device=pool.device)
+            masks = torch.empty((0, ACTION_SPACE), dtype=torch.bool, device=pool.device)
             meta = np.zeros((0, 8), dtype=np.int32)
+        return obs, masks, meta, (torch.cat(inv_parts) if (self.oracle and inv_parts) else None)
+
+    @staticmethod
+    def _slice_gameplays(games, obs, masks, meta, inv):
+        """games: per log dict(names, wanted, grp) -> list (per log) of lists of Gameplay (one per wanted seat)."""
         # order the samples of every (log, seat) like the reference: by event, the kan-select entry after its main entry
         order = np.lexsort((meta[:, 6], meta[:, 7], meta[:, 2], meta[:, 1])) if len(meta) else np.zeros(0, dtype=np.int64)
         meta = meta[order]
         idx_dev = torch.as_tensor(order, device=obs.device, dtype=torch.long)
         obs, masks = obs[idx_dev], masks[idx_dev]
-        inv = torch.cat(inv_parts)[idx_dev].cpu().numpy() if (self.oracle and inv_parts) else None
+        inv = inv[idx_dev].cpu().numpy() if inv is not None else None
         out = []
         pos = 0
         for t, g in enumerate(games):

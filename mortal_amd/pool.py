@@ -131,6 +131,24 @@ class TablePool:
 
         return _stat_call(call, self.n_tables, seats, per_seat)
 
+    def log_grp(self, table0=0, n=None, max_kyoku=64):
+        """dataset/grp.rs `Grp` of tables [table0, table0 + n) (n None = to the last), reduced from the device log in place
+        (mj_pool_grp; needs enable_log).  -> list of Grp, None for a table that is still playing or in error; ValueError for a
+        table whose log is malformed (or holds more than max_kyoku kyoku)."""
+        from .dataset import _grp_call
+
+        n = self.n_tables - table0 if n is None else int(n)
+
+        def call(*ptrs):
+            if self._L.mj_pool_grp(self.h, int(table0), n, int(max_kyoku), *ptrs, self._stream()) < 0:
+                raise MortalAmdError(self._L.mj_last_error().decode())
+
+        grps, n_kyoku, _counts = _grp_call(call, n, max_kyoku)
+        bad = np.flatnonzero(n_kyoku < 0)
+        if len(bad):
+            raise ValueError(f"table {table0 + int(bad[0])}: malformed event log (or more than {max_kyoku} kyoku)")
+        return grps
+
     # ---- log replay (dataset loader)
     def replay_load(self, scripts, tracked, always_include_kan_select=True, nonces=None, keys=None):
         """scripts: one uint64 word array per table (mjai_log.encode_events); tracked: 4-bit seat mask per table;
@@ -145,6 +163,25 @@ class TablePool:
         check(self._L.mj_replay_load(self.h, script.ctypes.data, off.ctypes.data, tr.ctypes.data, len(scripts),
                                  int(always_include_kan_select), n64.ctypes.data if n64 is not None else None,
                                  k64.ctypes.data if k64 is not None else None))
+
+    def replay_load_pool(self, src, table0=0, tracked=None, always_include_kan_select=True, deal_from_seed=False):
+        """Load the device logs of src's tables [table0, table0 + self.n_tables) as this pool's replay scripts, on the device
+        (mj_replay_load_pool; src needs enable_log).  tracked: 4-bit seat mask per table (None = all four seats);
+        deal_from_seed: the walls are rebuilt from the tables' seeds, which come with the logs (the invisible obs).
+        -> dict(loaded, skipped, malformed): a table still playing or in error is skipped, it replays as an empty log."""
+        tr = None
+        if tracked is not None:
+            tr = np.ascontiguousarray(tracked, dtype=np.uint8)
+            if tr.shape != (self.n_tables,):
+                raise ValueError(f"tracked: expected {self.n_tables} masks, got shape {tr.shape}")
+        if not isinstance(src, TablePool) or src._L is not self._L:
+            raise MortalAmdError("replay_load_pool: the source must be a pool of the same library")
+        counts = np.zeros(3, dtype=np.int64)
+        if self._L.mj_replay_load_pool(self.h, src.h, int(table0), tr.ctypes.data if tr is not None else None,
+                                       int(always_include_kan_select), int(deal_from_seed), counts.ctypes.data, self._stream()) < 0:
+            raise MortalAmdError(self._L.mj_last_error().decode())
+        self.n_rows = [0, 0]
+        return dict(loaded=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2]))
 
     def replay_step(self):
         check(self._L.mj_replay_step(self.h, self._stream()))
