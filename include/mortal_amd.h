@@ -28,6 +28,11 @@
  *   mj_replay_load_pool   arena/result.rs:32-51 dump_json_log -> dataset/gameplay.rs:66-124 load_gz_log_files (the log files between
  *                         self-play and the loader), without the files: the arena's device log is the loader's script
  *   mj_pool_grp, mj_grp_logs     dataset/grp.rs:90-164 Grp::load_events
+ *   mj_pool_enable_harvest, mj_harvest_pending, mj_harvest_take, mj_harvest_info / _games / _read / _destroy
+ *                         arena/game.rs:291-296 (a finished game's GameResult is handed over while the others play on) +
+ *                         arena/result.rs:19-51 (what a GameResult keeps: seed, scores, log)
+ *   mj_harvest_stat       stat.rs:263-441 + 443-498, as mj_pool_stat      mj_harvest_grp   dataset/grp.rs:90-164, as mj_pool_grp
+ *   mj_replay_load_harvest   arena/result.rs:32-51 -> dataset/gameplay.rs:66-124, as mj_replay_load_pool
  */
 #ifndef MORTAL_AMD_H
 #define MORTAL_AMD_H
@@ -120,7 +125,7 @@ int mj_replay_load(MjPool* pool, const uint64_t* script_host, const uint32_t* of
  * unknown event type is counted as malformed and gets an empty script too.  counts_out = {loaded, skipped, malformed}.
  * tracked_host: [dst n_tables] seat masks, NULL = all four seats.  deal_from_seed: every start_kyoku asks for the wall to be rebuilt
  * from the seed (LG_SK_DEAL_BIT) and dst's table t takes the seed of src's table table0 + t.  Needs mj_pool_enable_log on src;
- * an error if src is in refill mode (a restarted table's log has been rewound), if src == dst or if the range leaves src.  Ordered
+ * an error if src is in refill mode (a restarted table's log has been rewound; mj_replay_load_harvest is the route there), if src == dst or if the range leaves src.  Ordered
  * behind the steps of src already launched; synchronous; src is never modified.  Afterwards dst is where mj_replay_load leaves it. */
 int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tracked_host /* NULL ok */,
                         int always_include_kan_select, int deal_from_seed, int64_t counts_out[3], void* stream);
@@ -221,7 +226,7 @@ int mj_stat_logs(const uint64_t* words_host, const uint32_t* off_host /* [n_logs
                  int64_t counts_out[3], void* stream);
 /* The same over the pool's own device log, in place: every table whose game has finished (done == 1); running tables and
  * tables in error are skipped and counted.  group bit = agent_of_seat.  Needs mj_pool_enable_log; ordered behind the steps already
- * launched on `stream`; synchronous.  An error in refill mode: a restarted table's log has been rewound. */
+ * launched on `stream`; synchronous.  An error in refill mode: a restarted table's log has been rewound (mj_harvest_stat is the route there). */
 int mj_pool_stat(MjPool* pool, const uint8_t* seats_host /* [n_tables], NULL = all */, int64_t* totals_out,
                  int64_t* per_seat_out /* NULL or [n_tables][4][MJ_STAT_FIELDS] */, int64_t counts_out[3], void* stream);
 
@@ -237,10 +242,59 @@ int mj_grp_logs(const uint64_t* words_host, const uint32_t* off_host /* [n_logs 
                 int32_t* feat_out /* [n_logs][max_kyoku][7] */, int32_t* n_kyoku_out /* [n_logs] */, int32_t* rank_out /* [n_logs][4] */,
                 int32_t* final_out /* [n_logs][4] */, int64_t counts_out[3], void* stream);
 /* The same over tables [table0, table0 + n) of the pool's own device log, in place; tables are skipped as by mj_pool_stat (running, or
- * in error), a log_len beyond the log's capacity is malformed.  Needs mj_pool_enable_log; an error in refill mode; ordered behind the
- * steps already launched; synchronous. */
+ * in error), a log_len beyond the log's capacity is malformed.  Needs mj_pool_enable_log; an error in refill mode (mj_harvest_grp is the
+ * route there); ordered behind the steps already launched; synchronous. */
 int mj_pool_grp(MjPool* pool, int table0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
                 int32_t* final_out, int64_t counts_out[3], void* stream);
+
+/* ---- Finished games of a pool in refill mode (kernel: mortal_amd/csrc/mj_harvest.hip).  The reference's arena hands each GameResult
+ * over as its game finishes (arena/game.rs:291-296) and a GameResult keeps seed, scores and log (arena/result.rs:19-51).  Here a
+ * finished table is restarted in the next step and its log rewound; with harvesting enabled that step first copies the finished game
+ * -- log words, seed, final scores -- into the pool's active harvest buffer, on the device.  mj_harvest_take detaches the buffer as an
+ * MjHarvest; Stat, Grp and the replay loader then run on it like on a pool's log. */
+typedef struct MjHarvest MjHarvest;
+typedef struct MjHarvestGame {      /* one collected game */
+    uint64_t seed_nonce, seed_key;  /* the game's seed (board.rs:99-107) */
+    uint64_t first_word;            /* its log = words [first_word, first_word + n_words) of the harvest */
+    uint32_t n_words;               /* 0 for a game that ended in error or whose log overflowed: no words are kept */
+    uint32_t game_id;
+    uint32_t table;
+    uint32_t cycle;                 /* the pool's cycle index of the step that collected (and restarted) the table */
+    int32_t scores[4];              /* final scores, as mj_results reports them */
+    uint8_t err;                    /* the table's error code, 0 = none */
+    uint8_t agent_of_seat;
+    uint8_t reserved[6];
+} MjHarvestGame;                    /* 64 bytes */
+/* Allocate the active buffer: room for max_games records and max_words log words (a game takes its word count rounded up to even).
+ * Needs mj_pool_enable_log.  May be called before or after mj_pool_set_refill; games are collected only while the refill mode is on.
+ * A game that finds the buffer full is dropped and counted, nothing is overwritten, the table is restarted as usual.  Calling it again
+ * replaces the buffer (what it held is discarded); max_games 0 turns harvesting off again. */
+int mj_pool_enable_harvest(MjPool* pool, uint32_t max_games, uint64_t max_words);
+/* out = {games, words reserved, games dropped} in the active buffer right now (behind the steps already launched); one small copy. */
+int mj_harvest_pending(MjPool* pool, int64_t out[3], void* stream);
+/* Detach the active buffer as *out (which owns it; mj_harvest_destroy frees it) and give the pool a fresh one of the same size: later
+ * steps write into the replacement.  Ordered behind the steps already launched, whatever their stream; synchronous.  The records are
+ * copied to the host and sorted by (game_id, table): "game i" below is the i-th record of that order.  A table is collected by the step
+ * that restarts it, so a game that has finished but has not been restarted yet is not in this take: it is in the next one. */
+int mj_harvest_take(MjPool* pool, MjHarvest** out, void* stream);
+void mj_harvest_destroy(MjHarvest* h);
+/* out = {games, log words of all games, games dropped while this buffer was active, games in error}. */
+int mj_harvest_info(const MjHarvest* h, int64_t out[4]);
+int mj_harvest_games(const MjHarvest* h, MjHarvestGame* host_out /* [games], sorted */);
+/* The words of one game (the words mj_log_read returned for its table before the restart) to host memory, [n_words]. */
+int mj_harvest_read(const MjHarvest* h, int game, uint64_t* words_out);
+/* mj_pool_stat over the harvest: seats_host [games] (NULL = all), per_seat_out NULL or [games][4][MJ_STAT_FIELDS]; group bit = the
+ * record's agent_of_seat; a game in error is counted as skipped.  Synchronous. */
+int mj_harvest_stat(const MjHarvest* h, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
+                    void* stream);
+/* mj_pool_grp over games [game0, game0 + n) of the harvest. */
+int mj_harvest_grp(const MjHarvest* h, int game0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
+                   int32_t* final_out, int64_t counts_out[3], void* stream);
+/* mj_replay_load_pool from a harvest: log t of `dst` = game game0 + t, for all dst->n_tables tables; with deal_from_seed the seeds come
+ * from the records.  A game in error is skipped.  The destination is built beside dst and moved in last: a failing call leaves dst
+ * and the harvest as they were. */
+int mj_replay_load_harvest(MjPool* dst, const MjHarvest* h, int game0, const uint8_t* tracked_host /* NULL ok */,
+                           int always_include_kan_select, int deal_from_seed, int64_t counts_out[3], void* stream);
 
 /* First table in error: returns its error code (>0) and index, or 0. */
 int mj_pool_first_error(MjPool* pool, int* table_out, void* stream);

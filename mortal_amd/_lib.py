@@ -15,6 +15,8 @@ SYMBOLS = [
     "mj_encode_oracle", "mj_oracle_obs_rows", "mj_encode_timing", "mj_sp_timing", "mj_sp_phase_ticks", "mj_pool_set_sp_schedule", "mj_sp_schedule_stats", "mj_random_policy", "mj_greedy_policy", "mj_counters", "mj_results", "mj_pool_first_error", "mj_debug_table",
     "mj_debug_table_size", "mj_debug_layout", "mj_obs_rows", "mj_algo_query", "mj_stat_logs", "mj_pool_stat",
     "mj_replay_load_pool", "mj_grp_logs", "mj_pool_grp",
+    "mj_pool_enable_harvest", "mj_harvest_pending", "mj_harvest_take", "mj_harvest_destroy", "mj_harvest_info", "mj_harvest_games",
+    "mj_harvest_read", "mj_harvest_stat", "mj_harvest_grp", "mj_replay_load_harvest",
 ]
 
 
@@ -85,6 +87,17 @@ def _load(path=None):
     L.mj_replay_load_pool.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
     L.mj_grp_logs.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.mj_pool_grp.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.mj_pool_enable_harvest.argtypes = [vp, C.c_uint32, u64]
+    L.mj_harvest_pending.argtypes = [vp, vp, vp]
+    L.mj_harvest_take.argtypes = [vp, vp, vp]
+    L.mj_harvest_destroy.argtypes = [vp]
+    L.mj_harvest_destroy.restype = None
+    L.mj_harvest_info.argtypes = [vp, vp]
+    L.mj_harvest_games.argtypes = [vp, vp]
+    L.mj_harvest_read.argtypes = [vp, i32, vp]
+    L.mj_harvest_stat.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mj_harvest_grp.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.mj_replay_load_harvest.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
     return L
 
 

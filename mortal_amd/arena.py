@@ -77,12 +77,14 @@ def pack_reaction(ev):
     return int(ML.encode_events([ev])[0])
 
 
-class BatchRunner:
-    """Drives N tables to completion with up to two engines (agent 0 / agent 1)."""
+class _EngineRunner:
+    """What BatchRunner and SelfPlayRunner share: the engine checks, the pool the engines play on, and a cycle's answer of one agent."""
 
     pool_cls = TablePool  # the test suite substitutes the host emulation of the same kernels (tests/host/emu_pool.py)
+    keep_log = False
 
-    def __init__(self, engines, seeds, agent_of_seat, device=None, deal_algo=None, keep_log=False, keep_stat=False):
+    def _open_pool(self, engines, n, device, deal_algo):
+        """The engine checks and the pool they play on (shared with SelfPlayRunner)."""
         self.engines = engines
         self.cfg = [_check_engine(e) for e in engines]
         dev = device
@@ -91,46 +93,19 @@ class BatchRunner:
             dev = d0 if isinstance(d0, torch.device) and d0.type == "cuda" else torch.device(
                 f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cuda:0")
         self.device = torch.device(dev)
-        n = len(seeds)
         versions = [c["version"] for c in self.cfg if c["version"]] or [3]
         for c in self.cfg:
             c["version"] = c["version"] or versions[0]  # an mjai-log agent's rows are never encoded
         self.pool = self.pool_cls(n, version=self.cfg[0]["version"], deal_algo=deal_algo, device=str(self.device))
         self.device = self.pool.device
         self.any_mjai_log = any(c["mjai_log"] for c in self.cfg)
-        # mjai-log engines read the kyoku's events from the device log; keep_stat needs the log on the device and nothing else
-        # (no q-values, no per-decision metadata: those are keep_log's)
-        if keep_log or keep_stat or self.any_mjai_log:
-            self.pool.enable_log()
-        self.seeds = list(seeds)
-        self.agent_of_seat = np.asarray(agent_of_seat, dtype=np.uint8)
-        self.pool.reset(seeds, game_ids=np.arange(n), agent_of_seat=agent_of_seat, n_games_total=n)
+
+    def _configure_agents(self):
         for a, c in enumerate(self.cfg):
             self.pool.configure(a, enable_quick_eval=c["quick"], version=c["version"], enable_rule_based_agari_guard=c["guard"])
-        if len(engines) == 1:
+        if len(self.engines) == 1:
             self.pool.configure(1, enable_quick_eval=self.cfg[0]["quick"], version=self.cfg[0]["version"],
                                 enable_rule_based_agari_guard=self.cfg[0]["guard"])
-        # player planning of the reference (one_vs_three.rs:140-191, two_vs_two.rs:138-190): per agent the seats it plays,
-        # games in order, seats ascending; an mjai-log engine addresses its players by their index in that list
-        self.player_index = [{}, {}]
-        player_ids = [[], []]
-        for g in range(n):
-            for seat in range(4):
-                a = (int(self.agent_of_seat[g]) >> seat) & 1 if len(engines) > 1 else 0
-                self.player_index[a][(g, seat)] = len(player_ids[a])
-                player_ids[a].append(seat)
-        self._kyoku_ends = {}  # game -> end_kyoku events already reported to the mjai-log engines
-        self._log_cache = {}   # game -> (words decoded, events): the mjai-log agents' view of the device event log
-        self._lens, self._lens_cycle = None, -1
-        for a, eng in enumerate(engines):
-            if self.cfg[a]["mjai_log"]:
-                if callable(getattr(eng, "set_player_ids", None)):
-                    eng.set_player_ids(player_ids[a])
-                for idx in range(len(player_ids[a])):
-                    eng.start_game(idx)
-        self.cycles = 0
-        self.keep_log = keep_log
-        self.meta_batches = {}  # step index -> per agent (q_values, masks, is_greedy, eval_time_ns) of the rows it commits
 
     def _policy(self, agent, obs, masks, invisible=None):
         """-> (actions int32 cuda [n], q_values f32 cuda [n,46] or None).  q-values are kept only for a guarded agent."""
@@ -160,6 +135,62 @@ class BatchRunner:
                                np.asarray(_m, dtype=bool).reshape(-1, ACTION_SPACE), np.asarray(_g, dtype=bool).reshape(-1))
         q = torch.as_tensor(q_values, dtype=torch.float32, device=self.device).contiguous() if guard else None
         return torch.as_tensor(actions, dtype=torch.int32, device=self.device), q
+
+
+    def _answer(self, a, n_rows):
+        """Agent a's batch of this cycle encoded, put to its engine and checked -> (actions, q-values or None, the engine's ns)."""
+        pool = self.pool
+        obs, masks = pool.encode(a)
+        inv = pool.encode_oracle(a) if self.cfg[min(a, len(self.cfg) - 1)]["oracle"] else None
+        self._last_meta = None
+        t0 = time.perf_counter_ns()
+        acts, qs = self._policy(a, obs, masks, inv)
+        if acts.numel() != n_rows or (qs is not None and tuple(qs.shape) != (n_rows, ACTION_SPACE)):
+            raise RuntimeError(f"engine returned {acts.numel()} actions"
+                               + (f" / q-values of shape {tuple(qs.shape)}" if qs is not None else "")
+                               + f" for a batch of {n_rows} rows")
+        return acts, qs, time.perf_counter_ns() - t0
+
+
+    def close(self):
+        self.pool.close()
+
+
+class BatchRunner(_EngineRunner):
+    """Drives N tables to completion with up to two engines (agent 0 / agent 1)."""
+
+    def __init__(self, engines, seeds, agent_of_seat, device=None, deal_algo=None, keep_log=False, keep_stat=False):
+        n = len(seeds)
+        self._open_pool(engines, n, device, deal_algo)
+        # mjai-log engines read the kyoku's events from the device log; keep_stat needs the log on the device and nothing else
+        # (no q-values, no per-decision metadata: those are keep_log's)
+        if keep_log or keep_stat or self.any_mjai_log:
+            self.pool.enable_log()
+        self.seeds = list(seeds)
+        self.agent_of_seat = np.asarray(agent_of_seat, dtype=np.uint8)
+        self.pool.reset(seeds, game_ids=np.arange(n), agent_of_seat=agent_of_seat, n_games_total=n)
+        self._configure_agents()
+        # player planning of the reference (one_vs_three.rs:140-191, two_vs_two.rs:138-190): per agent the seats it plays,
+        # games in order, seats ascending; an mjai-log engine addresses its players by their index in that list
+        self.player_index = [{}, {}]
+        player_ids = [[], []]
+        for g in range(n):
+            for seat in range(4):
+                a = (int(self.agent_of_seat[g]) >> seat) & 1 if len(engines) > 1 else 0
+                self.player_index[a][(g, seat)] = len(player_ids[a])
+                player_ids[a].append(seat)
+        self._kyoku_ends = {}  # game -> end_kyoku events already reported to the mjai-log engines
+        self._log_cache = {}   # game -> (words decoded, events): the mjai-log agents' view of the device event log
+        self._lens, self._lens_cycle = None, -1
+        for a, eng in enumerate(engines):
+            if self.cfg[a]["mjai_log"]:
+                if callable(getattr(eng, "set_player_ids", None)):
+                    eng.set_player_ids(player_ids[a])
+                for idx in range(len(player_ids[a])):
+                    eng.start_game(idx)
+        self.cycles = 0
+        self.keep_log = keep_log
+        self.meta_batches = {}  # step index -> per agent (q_values, masks, is_greedy, eval_time_ns) of the rows it commits
 
     def _fail(self, code, tbl):
         """Illegal action / rule violation on table `tbl`: the reference aborts the whole run with the offending event and
@@ -299,18 +330,10 @@ class BatchRunner:
                 if self.cfg[min(a, len(self.cfg) - 1)]["mjai_log"]:
                     evs[a] = self._mjai_log_policy(min(a, len(self.cfg) - 1))
                     continue
-                obs, masks = pool.encode(a)
-                inv = pool.encode_oracle(a) if self.cfg[min(a, len(self.cfg) - 1)]["oracle"] else None
-                self._last_meta = None
-                t0 = time.perf_counter_ns()
-                acts[a], qs[a] = self._policy(a, obs, masks, inv)
-                if acts[a].numel() != n[a] or (qs[a] is not None and tuple(qs[a].shape) != (n[a], ACTION_SPACE)):
-                    raise RuntimeError(f"engine returned {acts[a].numel()} actions"
-                                       + (f" / q-values of shape {tuple(qs[a].shape)}" if qs[a] is not None else "")
-                                       + f" for a batch of {n[a]} rows")
+                acts[a], qs[a], eval_ns = self._answer(a, n[a])
                 if self.keep_log and self._last_meta is not None:
                     # these rows are committed by the NEXT mj_step call, whose index the device writes into the log tags
-                    self.meta_batches.setdefault(self.cycles, {})[a] = self._last_meta + (time.perf_counter_ns() - t0,)
+                    self.meta_batches.setdefault(self.cycles, {})[a] = self._last_meta + (eval_ns,)
         if progress is not None:
             report(final=True)
         code, tbl = pool.first_error()
@@ -401,8 +424,94 @@ class BatchRunner:
             paths.append(mjai_log.write_game_log_as(os.path.join(log_dir, name), names, self.seeds[g], events))
         return paths
 
-    def close(self):
-        self.pool.close()
+
+class SelfPlayRunner(_EngineRunner):
+    """Self-play at full occupancy with the samples out, no files: a pool in refill mode whose finished games are collected on
+    the device (TablePool.enable_harvest) while the other tables play on.  The reference loops over play, collect and load
+    (mortal/client.py:35, player.py:120-157) and its arena hands each GameResult over as the game finishes
+    (arena/game.rs:291-296); here `play` returns a Harvest whenever enough games are in, and `gameplays` / `stats` read it.
+    An extension of this engine: the reference has no restarting arena.
+
+    Table t plays seed (seed_start[0] + t + g * nonce_stride, seed_start[1]) and game id t + g * n_tables in its generation g
+    (nonce_stride defaults to n_tables: no seed is played twice).  agent_of_seat [n_tables]: bit s = engine of seat s; a table
+    keeps its agent_of_seat for every generation it plays.  stagger: the tables enter play spread over that many cycles
+    (TablePool.set_start_stagger; a table's first game is then generation 1).  max_games / max_words size the harvest buffer: a
+    game that finds it full is dropped and counted (Harvest.dropped), so take often enough.
+
+    A table in error does not raise: its game is reported through its record (err, no words) and the table restarts like any
+    other -- a long run must survive one bad answer.  Engines that answer with mjai events are refused."""
+
+    def __init__(self, engines, n_tables, seed_start, agent_of_seat=None, *, nonce_stride=None, stagger=0, max_games, max_words,
+                 deal_algo=None, device=None):
+        n = int(n_tables)
+        self._open_pool(engines, n, device, deal_algo)
+        try:
+            if self.any_mjai_log:
+                raise ValueError("SelfPlayRunner: engines that answer with mjai events (engine_type 'mjai-log') are not supported: "
+                                 "they are told about every game's start and end one by one, which a restarting pool does not do; "
+                                 "use BatchRunner")
+            self.seeds = [(int(seed_start[0]) + t, int(seed_start[1])) for t in range(n)]
+            self.agent_of_seat = np.zeros(n, dtype=np.uint8) if agent_of_seat is None else np.asarray(agent_of_seat, dtype=np.uint8)
+            if self.agent_of_seat.shape != (n,):
+                raise ValueError(f"agent_of_seat: expected {n} masks, got shape {self.agent_of_seat.shape}")
+            self.nonce_stride = n if nonce_stride is None else int(nonce_stride)
+            if self.nonce_stride <= 0:
+                raise ValueError("nonce_stride must be positive")
+            self.pool.enable_log()
+            self.pool.reset(self.seeds, game_ids=np.arange(n), agent_of_seat=self.agent_of_seat, n_games_total=n)
+            self._configure_agents()
+            self.pool.set_refill(self.nonce_stride)
+            if stagger:
+                self.pool.set_start_stagger(int(stagger))
+            self.pool.enable_harvest(int(max_games), int(max_words))
+        except BaseException:
+            self.pool.close()
+            raise
+        self.cycles = 0
+        self.keep_log = False
+        self._acts, self._qs = [None, None], [None, None]
+
+    def play(self, min_games, max_cycles=None, on_step=None, check_every=16):
+        """Step until at least min_games finished games are collected, then take them -> Harvest (the caller closes it; games
+        that finish later are in the next one).  The count of collected games costs a copy from the device and a stream
+        synchronise, so it is read every check_every cycles only: the harvest may hold the few games more that finished in
+        between.  max_cycles bounds this call.  on_step(runner) is called after every step."""
+        pool = self.pool
+        start = self.cycles
+        check_every = max(1, int(check_every))
+        while (self.cycles - start) % check_every or pool.harvest_pending()["games"] < min_games:
+            if max_cycles is not None and self.cycles - start >= max_cycles:
+                raise MortalAmdError(f"play: max_cycles exceeded with {pool.harvest_pending()['games']} of {min_games} games collected")
+            n = pool.step(self._acts[0], self._acts[1], self._qs[0], self._qs[1])
+            self.cycles += 1
+            if on_step is not None:
+                on_step(self)
+            self._acts, self._qs = [None, None], [None, None]
+            for a in (0, 1):
+                if n[a]:
+                    self._acts[a], self._qs[a], _ns = self._answer(a, n[a])
+        if pool.counters()["sp_overflow"]:
+            raise MortalAmdError("obs v4: a decision's single-player state graph exceeded the device scratch capacity "
+                                 "(SP_CAP in mortal_amd/csrc/mj_sp.hip); its SP planes would be incomplete")
+        return pool.take_harvest()
+
+    def _names(self, harvest):
+        names_of_agent = [c["name"] for c in self.cfg]
+        if len(names_of_agent) == 1:
+            names_of_agent = names_of_agent * 2
+        return [[names_of_agent[(int(m) >> s) & 1] for s in range(4)] for m in harvest.games["agent_of_seat"]]
+
+    def gameplays(self, loader, harvest, seats=None):
+        """The training samples of every game of the harvest (GameplayLoader.load_harvest) -> a list per game of Gameplay, one per
+        wanted seat, the seats named by engine as BatchRunner.gameplays names them.  seats: 4-bit seat mask per game."""
+        return loader.load_harvest(harvest, seats=seats, names=self._names(harvest))
+
+    def stats(self, harvest):
+        """{engine name: Stat} over the games of the harvest (games in error are left out)."""
+        totals, _rows, counts = harvest.stat()
+        if counts["malformed"]:
+            raise MortalAmdError(f"stats: {counts['malformed']} malformed logs")
+        return _stats_by_name([c["name"] for c in self.cfg], [t.counters() for t in totals])
 
 
 def _stats_by_name(names, agent_counters):

@@ -1,5 +1,5 @@
 // C-ABI host side (include/mortal_amd.h): pool life-cycle and kernel launches.  One translation unit for the whole
-// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip / mj_gameplay.hip.
+// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip / mj_gameplay.hip / mj_harvest.hip.
 // Host float math below builds bit-exact LUTs: compile with -ffp-contract=off.
 // Ownership: whatever the host takes from the HIP runtime is held by an owner of mj_host.h and released by its destructor; a call that
 // returns an error leaves the pool as it was before the call (a fallible call builds into locals and moves them in as its last step).
@@ -22,6 +22,7 @@
 #include "mj_sp.hip"
 #include "mj_stat.hip"
 #include "mj_gameplay.hip"
+#include "mj_harvest.hip"
 
 static_assert(sizeof(MjAlgoQuery) == 72, "MjAlgoQuery layout");
 // include/mortal_amd.h mj_algo_query: one thread per query, the same device functions the step / encode / SP kernels call
@@ -222,6 +223,19 @@ struct ReplayBufs {  // log replay (dataset loader): built by mj_replay_load, mo
     int always_kan = 1;
 };
 
+struct HarvestBuf {  // a harvest buffer (mj_harvest.hip): the pool's active one, or the one an MjHarvest took with it
+    DevBuf<MjHarvestGame> games;
+    DevBuf<uint64_t> words;
+    DevBuf<unsigned long long> cursors;  // [HV_CURSORS]
+    uint64_t max_games = 0, max_words = 0;
+    int alloc(uint64_t n_games, uint64_t n_words, hipStream_t s) {  // empty, its cursors zeroed on s
+        if (games.alloc(n_games) || words.alloc(n_words + 2) || cursors.alloc(HV_CURSORS)) return -1;
+        HIP_OK(hipMemsetAsync(cursors.get(), 0, HV_CURSORS * sizeof(unsigned long long), s));
+        max_games = n_games, max_words = n_words;
+        return 0;
+    }
+};
+
 std::vector<MjGatherEnt> build_gather() {
     std::vector<MjGatherEnt> v;
 #define MJ_X_GATHER(type, name, dims, count)                                                         \
@@ -267,6 +281,7 @@ struct MjPool {
     int enable_agari_guard[2] = {0, 0};
     uint64_t refill_stride = 0;
     uint32_t start_stagger = 0;
+    HarvestBuf hv;                  // active harvest buffer (mj_pool_enable_harvest); filled by mj_k_harvest while the refill mode is on
     uint64_t cycles = 0;
     int last_rows[2] = {0, 0};
     bool rows_valid = false;
@@ -573,6 +588,11 @@ int mj_step_ev(MjPool* P, const int32_t* a0, const int32_t* a1, const float* q0,
     sp.final_done = P->final_done.get();
     sp.n_games_total = P->n_games_total;
     sp.block_rows = P->block_rows.get();
+    if (sp.refill && P->hv.games && P->log) {  // what mj_k_refill is about to rewind goes to the harvest buffer first
+        const HarvestParams hp = {P->blocks.get(), P->n_tables, sp.cycle, sp.start_stagger, P->log.get(), P->log_len.get(), P->log_cap,
+                                  P->hv.games.get(), P->hv.words.get(), P->hv.cursors.get(), P->hv.max_games, P->hv.max_words};
+        hipLaunchKernelGGL(mj_k_harvest, dim3(P->n_blocks), dim3(64), 0, s, hp);
+    }
     if (sp.refill) hipLaunchKernelGGL(mj_k_refill, dim3(P->n_blocks), dim3(64), 0, s, sp);
     hipLaunchKernelGGL(mj_k_step, dim3(P->n_blocks), dim3(MJ_LANES), 0, s, sp);
     return launch_rows(P, s);
@@ -1168,7 +1188,7 @@ int mj_pool_stat(MjPool* P, const uint8_t* seats_host, int64_t* totals_out, int6
                  void* stream) {
     if (!P) return fail("null pool");
     if (!P->log) return fail("mj_pool_stat: the event log is not enabled (mj_pool_enable_log)");
-    if (P->refill_stride) return fail("mj_pool_stat: not available in refill mode (a restarted table's log has been rewound)");
+    if (P->refill_stride) return fail("mj_pool_stat: not available in refill mode (a restarted table's log has been rewound; mj_harvest_stat reads collected games)");
     hipStream_t s = (hipStream_t)stream;
     if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));  // behind the last step, whatever its stream
     StatParams K{};
@@ -1256,7 +1276,7 @@ int mj_pool_grp(MjPool* P, int table0, int n, int max_kyoku, int32_t* feat_out, 
     if (!P) return fail("null pool");
     if (grp_args("mj_pool_grp", n, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out)) return -1;
     if (!P->log) return fail("mj_pool_grp: the event log is not enabled (mj_pool_enable_log)");
-    if (P->refill_stride) return fail("mj_pool_grp: not available in refill mode (a restarted table's log has been rewound)");
+    if (P->refill_stride) return fail("mj_pool_grp: not available in refill mode (a restarted table's log has been rewound; mj_harvest_grp reads collected games)");
     if (table0 < 0 || table0 > P->n_tables - n) return fail("mj_pool_grp: table range out of bounds");
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -1264,19 +1284,19 @@ int mj_pool_grp(MjPool* P, int table0, int n, int max_kyoku, int32_t* feat_out, 
     return grp_run(pool_log_src(P, table0, n), max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out, s);
 }
 
-int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tracked_host, int always_include_kan_select,
-                        int deal_from_seed, int64_t counts_out[3], void* stream) {
-    if (!dst || !src) return fail("null pool");
-    if (!counts_out) return fail("mj_replay_load_pool: null counts buffer");
-    memset(counts_out, 0, 3 * sizeof(int64_t));
-    if (src == dst) return fail("mj_replay_load_pool: the source pool cannot be its own destination (the load restarts the destination's tables)");
-    if (!src->log) return fail("mj_replay_load_pool: the event log of the source pool is not enabled (mj_pool_enable_log)");
-    if (src->refill_stride) return fail("mj_replay_load_pool: not available in refill mode (a restarted table's log has been rewound)");
+namespace {
+// where the destination's tables take their seeds from (deal_from_seed): the source pool's tables, or plain device arrays
+struct SeedSrc {
+    const TableBlock* blocks;
+    int table0;
+    const uint64_t *nonces, *keys;
+};
+// The load shared by mj_replay_load_pool and mj_replay_load_harvest: the logs of S become dst's replay scripts, on the device.
+// Everything is built beside the destination and moved in last: its tables and counters too, so that no failure -- the last
+// synchronise included -- can leave it between two scripts.
+int replay_load_src(const std::string& who, MjPool* dst, const LogSrc& S, const SeedSrc& seeds, const uint8_t* tracked_host,
+                    int always_include_kan_select, int deal_from_seed, int64_t counts_out[3], hipStream_t s) {
     const int n = dst->n_tables;
-    if (table0 < 0 || table0 > src->n_tables - n) return fail("mj_replay_load_pool: table range out of bounds");
-    hipStream_t s = (hipStream_t)stream;
-    // everything is built beside the destination and moved in last: its tables and counters too, so that no failure -- the last
-    // synchronise included -- can leave it between two scripts
     ReplayBufs R;
     DevBuf<TableBlock> blocks;
     DevBuf<unsigned long long> counters, sums;  // sums: loaded / skipped / malformed, total words
@@ -1294,20 +1314,18 @@ int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tra
     HIP_OK(hipMemsetAsync(counters.get(), 0, 8 * sizeof(unsigned long long), s));
     HIP_OK(hipMemsetAsync(sums.get(), 0, 4 * sizeof(unsigned long long), s));
     R.always_kan = always_include_kan_select;
-    if (src->ev_snap && s != src->step_stream) HIP_OK(hipStreamWaitEvent(s, src->ev_snap.get(), 0));  // behind the source's last step
-    const LogSrc S = pool_log_src(src, table0, n);
     const int grid = log_grid((size_t)n);
     const LogLenParams lp = {S, len.get(), sums.get()};
     hipLaunchKernelGGL(mj_k_log_len, dim3(grid), dim3(LOGK_THREADS), 0, s, lp);
     hipLaunchKernelGGL(mj_k_log_scan, dim3(1), dim3(1024), 0, s, len.get(), n, R.off.get(), sums.get() + 3);
-    const TableBlock* seeds_of = deal_from_seed ? src->blocks.get() : nullptr;
-    hipLaunchKernelGGL(mj_k_log_fresh, dim3(dst->n_blocks), dim3(64), 0, s, blocks.get(), n, seeds_of, table0);
+    const SeedSrc sd = deal_from_seed ? seeds : SeedSrc{nullptr, 0, nullptr, nullptr};
+    hipLaunchKernelGGL(mj_k_log_fresh, dim3(dst->n_blocks), dim3(64), 0, s, blocks.get(), n, sd.blocks, sd.table0, sd.nonces, sd.keys);
     HIP_OK(hipGetLastError());
     unsigned long long sums_host[4];
     HIP_OK(hipMemcpyAsync(sums_host, sums.get(), sizeof sums_host, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     if (sums_host[3] > 0xFFFFFFFFull)
-        return fail("mj_replay_load_pool: " + std::to_string(sums_host[3]) + " script words do not fit the 32-bit offsets: load fewer tables per call");
+        return fail(who + ": " + std::to_string(sums_host[3]) + " script words do not fit the 32-bit offsets: load fewer tables per call");
     if (R.script.alloc((size_t)sums_host[3] + 1)) return -1;
     const LogPackParams pp = {S, R.off.get(), R.script.get(), deal_from_seed};
     hipLaunchKernelGGL(mj_k_log_pack, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
@@ -1321,6 +1339,170 @@ int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tra
     dst->cycles = 0;
     dst->rows_valid = false;
     return 0;
+}
+}  // namespace
+
+int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tracked_host, int always_include_kan_select,
+                        int deal_from_seed, int64_t counts_out[3], void* stream) {
+    if (!dst || !src) return fail("null pool");
+    if (!counts_out) return fail("mj_replay_load_pool: null counts buffer");
+    memset(counts_out, 0, 3 * sizeof(int64_t));
+    if (src == dst) return fail("mj_replay_load_pool: the source pool cannot be its own destination (the load restarts the destination's tables)");
+    if (!src->log) return fail("mj_replay_load_pool: the event log of the source pool is not enabled (mj_pool_enable_log)");
+    if (src->refill_stride)
+        return fail("mj_replay_load_pool: not available in refill mode (a restarted table's log has been rewound; mj_replay_load_harvest loads collected games)");
+    const int n = dst->n_tables;
+    if (table0 < 0 || table0 > src->n_tables - n) return fail("mj_replay_load_pool: table range out of bounds");
+    hipStream_t s = (hipStream_t)stream;
+    if (src->ev_snap && s != src->step_stream) HIP_OK(hipStreamWaitEvent(s, src->ev_snap.get(), 0));  // behind the source's last step
+    return replay_load_src("mj_replay_load_pool", dst, pool_log_src(src, table0, n), SeedSrc{src->blocks.get(), table0, nullptr, nullptr},
+                           tracked_host, always_include_kan_select, deal_from_seed, counts_out, s);
+}
+
+// ---------------------------------------------------------------- finished games of a refilling pool (mj_harvest.hip)
+struct MjHarvest {
+    HarvestBuf buf;                    // the detached buffer: records in arrival order, words
+    std::vector<MjHarvestGame> games;  // the records sorted by (game_id, table); the arrays below are in this order
+    DevBuf<uint64_t> start, nonce, key;
+    DevBuf<uint32_t> len;
+    DevBuf<uint8_t> group;             // agent_of_seat
+    int64_t n_words = 0, dropped = 0, n_err = 0;
+};
+
+int mj_pool_enable_harvest(MjPool* P, uint32_t max_games, uint64_t max_words) {
+    if (!P) return fail("null pool");
+    if (!P->log) return fail("mj_pool_enable_harvest: the event log is not enabled (mj_pool_enable_log)");
+    hipStream_t s = P->step_stream;
+    HarvestBuf B;  // (max_games 0: none -- harvesting is turned off)
+    if (max_games && B.alloc(max_games, max_words & ~1ull, s)) return -1;
+    HIP_OK(hipStreamSynchronize(s));  // behind the steps that may still be writing the buffer that goes
+    P->hv = std::move(B);
+    return 0;
+}
+
+int mj_harvest_pending(MjPool* P, int64_t out[3], void* stream) {
+    if (!P || !out) return fail("null pool / output");
+    if (!P->hv.games) return fail("mj_harvest_pending: harvesting is not enabled (mj_pool_enable_harvest)");
+    hipStream_t s = (hipStream_t)stream;
+    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));
+    unsigned long long c[HV_CURSORS];
+    HIP_OK(hipMemcpyAsync(c, P->hv.cursors.get(), sizeof c, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    out[0] = (int64_t)c[HV_GAMES], out[1] = (int64_t)c[HV_WORDS], out[2] = (int64_t)c[HV_DROPPED];
+    return 0;
+}
+
+int mj_harvest_take(MjPool* P, MjHarvest** out, void* stream) {
+    if (!P || !out) return fail("null pool / output");
+    *out = nullptr;
+    if (!P->hv.games) return fail("mj_harvest_take: harvesting is not enabled (mj_pool_enable_harvest)");
+    hipStream_t s = (hipStream_t)stream;
+    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));  // behind the last step, whatever its stream
+    // the replacement first; the pool keeps its buffer until nothing can fail any more
+    HarvestBuf fresh;
+    if (fresh.alloc(P->hv.max_games, P->hv.max_words, s)) return -1;
+    std::unique_ptr<MjHarvest> H(new MjHarvest);
+    unsigned long long c[HV_CURSORS];
+    HIP_OK(hipMemcpyAsync(c, P->hv.cursors.get(), sizeof c, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    const size_t n = (size_t)std::min<unsigned long long>(c[HV_GAMES], P->hv.max_games);
+    H->games.resize(n);
+    if (n) HIP_OK(hipMemcpyAsync(H->games.data(), P->hv.games.get(), n * sizeof(MjHarvestGame), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    std::sort(H->games.begin(), H->games.end(), [](const MjHarvestGame& a, const MjHarvestGame& b) {
+        return a.game_id != b.game_id ? a.game_id < b.game_id : a.table < b.table;
+    });
+    std::vector<uint64_t> start(n), nonce(n), key(n);
+    std::vector<uint32_t> len(n);
+    std::vector<uint8_t> group(n);
+    for (size_t i = 0; i < n; i++) {
+        const MjHarvestGame& g = H->games[i];
+        if (g.first_word > P->hv.max_words || g.n_words > P->hv.max_words - g.first_word)
+            return fail("mj_harvest_take: record " + std::to_string(i) + " points outside the buffer");
+        start[i] = g.first_word, len[i] = g.n_words, nonce[i] = g.seed_nonce, key[i] = g.seed_key, group[i] = g.agent_of_seat;
+        H->n_words += g.n_words;
+        H->n_err += g.err != 0;
+    }
+    H->dropped = (int64_t)c[HV_DROPPED];
+    if (stat_upload(H->start, start.data(), n, s) || stat_upload(H->len, len.data(), n, s) || stat_upload(H->nonce, nonce.data(), n, s) ||
+        stat_upload(H->key, key.data(), n, s) || stat_upload(H->group, group.data(), n, s))
+        return -1;
+    HIP_OK(hipStreamSynchronize(s));
+    std::swap(P->hv, fresh);          // later steps write into the replacement ...
+    H->buf = std::move(fresh);        // ... and the filled buffer leaves with the harvest
+    *out = H.release();
+    return 0;
+}
+
+void mj_harvest_destroy(MjHarvest* h) { delete h; }
+
+int mj_harvest_info(const MjHarvest* h, int64_t out[4]) {
+    if (!h || !out) return fail("null harvest / output");
+    out[0] = (int64_t)h->games.size(), out[1] = h->n_words, out[2] = h->dropped, out[3] = h->n_err;
+    return 0;
+}
+int mj_harvest_games(const MjHarvest* h, MjHarvestGame* host_out) {
+    if (!h) return fail("null harvest");
+    if (h->games.size() && !host_out) return fail("mj_harvest_games: null output");
+    if (h->games.size()) memcpy(host_out, h->games.data(), h->games.size() * sizeof(MjHarvestGame));
+    return 0;
+}
+int mj_harvest_read(const MjHarvest* h, int game, uint64_t* words_out) {
+    if (!h) return fail("null harvest");
+    if (game < 0 || (size_t)game >= h->games.size()) return fail("mj_harvest_read: game " + std::to_string(game) + " is not in the harvest");
+    const MjHarvestGame& g = h->games[game];
+    if (g.n_words == 0) return 0;
+    if (!words_out) return fail("mj_harvest_read: null output");
+    HIP_OK(hipMemcpy(words_out, h->buf.words.get() + g.first_word, (size_t)g.n_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mj_harvest_stat(const MjHarvest* h, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
+                    void* stream) {
+    if (!h) return fail("null harvest");
+    if (!totals_out || !counts_out) return fail("null totals / counts buffer");
+    memset(totals_out, 0, 2 * MJ_STAT_FIELDS * sizeof(int64_t));
+    memset(counts_out, 0, 3 * sizeof(int64_t));
+    if (h->games.empty()) return 0;
+    StatParams K{};
+    K.words = h->buf.words.get();
+    K.start = h->start.get();
+    K.len = h->len.get();
+    K.groups = h->group.get();
+    K.n_logs = (int)h->games.size();
+    return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, (hipStream_t)stream);
+}
+
+namespace {
+LogSrc harvest_log_src(const MjHarvest* h, int game0, int n) {
+    LogSrc S{};
+    S.words = h->buf.words.get();
+    S.start = h->start.get() + game0;
+    S.len = h->len.get() + game0;
+    S.n_logs = n;
+    return S;
+}
+}  // namespace
+
+int mj_harvest_grp(const MjHarvest* h, int game0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
+                   int32_t* final_out, int64_t counts_out[3], void* stream) {
+    if (!h) return fail("null harvest");
+    if (grp_args("mj_harvest_grp", n, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out)) return -1;
+    if (game0 < 0 || game0 > (int)h->games.size() - n) return fail("mj_harvest_grp: game range out of bounds");
+    if (n == 0) return 0;
+    return grp_run(harvest_log_src(h, game0, n), max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out, (hipStream_t)stream);
+}
+
+int mj_replay_load_harvest(MjPool* dst, const MjHarvest* h, int game0, const uint8_t* tracked_host, int always_include_kan_select,
+                           int deal_from_seed, int64_t counts_out[3], void* stream) {
+    if (!dst || !h) return fail("null pool / harvest");
+    if (!counts_out) return fail("mj_replay_load_harvest: null counts buffer");
+    memset(counts_out, 0, 3 * sizeof(int64_t));
+    const int n = dst->n_tables;
+    if (game0 < 0 || game0 > (int)h->games.size() - n) return fail("mj_replay_load_harvest: game range out of bounds");
+    return replay_load_src("mj_replay_load_harvest", dst, harvest_log_src(h, game0, n),
+                           SeedSrc{nullptr, 0, h->nonce.get() + game0, h->key.get() + game0}, tracked_host, always_include_kan_select,
+                           deal_from_seed, counts_out, (hipStream_t)stream);
 }
 
 __global__ void mj_k_first_error(const TableBlock* blocks, int n_tables, unsigned long long* out) {

@@ -22,7 +22,8 @@
 #define LOGK_GRID_MAX (256 * 4)      // bounded grid, the rest by grid stride (MJ_LOG_GRID lowers it: tests)
 #define LOGK_WINDOW_LAST 60          // mj_k_log_grp: header + tag + two payload words <= window index 63
 
-// The two addressings of StatParams: concatenated logs with `off`, or tables [table0, table0 + n_logs) of a pool's strided log.
+// The three addressings of StatParams: concatenated logs with `off`, tables [table0, table0 + n_logs) of a pool's strided log, or
+// scattered logs of a harvest (mj_harvest.hip) with `start`.
 struct LogSrc {
     const uint64_t* words;
     const uint32_t* off;         // [n_logs + 1], or NULL: log i is table table0 + i, at words + table * stride ...
@@ -31,6 +32,7 @@ struct LogSrc {
     const TableBlock* blocks;    // pool path: flags / err of the table
     int table0;
     int n_logs;
+    const uint64_t* start;       // [n_logs], or NULL; scattered: log i is words + start[i] with len[i] words, len[i] == 0 = skipped
 };
 enum { LOG_OK = 0, LOG_SKIP = 1, LOG_BAD = 2 };
 
@@ -40,6 +42,11 @@ MJD int log_locate(const LogSrc& S, int i, const uint64_t*& lw, uint32_t& len) {
     if (S.off) {
         lw = S.words + (size_t)S.off[i];
         len = S.off[i + 1] - S.off[i];
+        return len ? LOG_OK : LOG_SKIP;
+    }
+    if (S.start) {
+        lw = S.words + (size_t)S.start[i];
+        len = S.len[i];
         return len ? LOG_OK : LOG_SKIP;
     }
     const int t = S.table0 + i;
@@ -159,8 +166,10 @@ __global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_pack(LogPackParams P) {
 }
 
 // ---- the destination's tables at the start of a replay (mj_capi.hip fresh_blocks, on the device): `fresh` arrives zeroed; the
-// padding lanes of the last block are inactive; with `src`, table i takes the seed of the source's table table0 + i
-__global__ __launch_bounds__(64) void mj_k_log_fresh(TableBlock* fresh, int n_tables, const TableBlock* src, int table0) {
+// padding lanes of the last block are inactive; with `src`, table i takes the seed of the source's table table0 + i; with plain
+// `nonces` / `keys` arrays (a harvest's records), table i takes nonces[i], keys[i]
+__global__ __launch_bounds__(64) void mj_k_log_fresh(TableBlock* fresh, int n_tables, const TableBlock* src, int table0,
+                                                     const uint64_t* nonces, const uint64_t* keys) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     TableBlock* B = fresh + blockIdx.x;
     const int l = threadIdx.x;
@@ -170,6 +179,9 @@ __global__ __launch_bounds__(64) void mj_k_log_fresh(TableBlock* fresh, int n_ta
         const int t = table0 + i;
         B->seed_nonce[l] = src[t >> 6].seed_nonce[t & 63];
         B->seed_key[l] = src[t >> 6].seed_key[t & 63];
+    } else if (nonces) {
+        B->seed_nonce[l] = nonces[i];
+        B->seed_key[l] = keys[i];
     }
 }
 

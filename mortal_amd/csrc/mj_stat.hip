@@ -36,6 +36,7 @@ struct StatParams {
     unsigned long long* totals;  // [2][MJ_STAT_FIELDS], added to
     long long* per_seat;         // NULL or [n_logs][4][MJ_STAT_FIELDS], every row written
     unsigned long long* counts;  // [3] logs reduced / skipped / malformed, added to
+    const uint64_t* start;       // [n_logs], or NULL; scattered (off NULL): log i starts at start[i] and has len[i] words, 0 = skipped
 };
 
 MJD int stat_pick(int s, int v0, int v1, int v2, int v3) { return s == 0 ? v0 : s == 1 ? v1 : s == 2 ? v2 : v3; }
@@ -59,6 +60,9 @@ __global__ __launch_bounds__(STAT_THREADS) void mj_k_log_stat(StatParams P) {
         if (P.off) {
             lw = P.words + (size_t)P.off[log];
             len = P.off[log + 1] - P.off[log];
+        } else if (P.start) {
+            lw = P.words + (size_t)P.start[log];
+            len = P.len[log];
         } else {
             lw = P.words + (size_t)log * P.stride;
             len = min(P.len[log], P.stride);

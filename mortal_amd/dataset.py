@@ -400,12 +400,30 @@ class GameplayLoader:
 
         Memory: all obs of the range are materialised on the device at once (137 KB per obs-v4 sample, about 600 samples per
         game and seat), so the caller bounds memory by the table range it asks for."""
+        return self._load_device("load_pool", "tables", "pool", pool.n_tables, table0, n_tables, seats, names, type(pool), pool,
+                                 pool.log_grp, lambda rp, first, tracked: rp.replay_load_pool(
+                                     pool, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle))
+
+    def load_harvest(self, harvest, game0=0, n_games=None, seats=None, names=None):
+        """The samples of the games a pool in refill mode has collected (TablePool.take_harvest), with the contract of load_pool:
+        games [game0, game0 + n_games) of the harvest's sorted order (None = to the last) are replayed on the device from the
+        collected words (mj_replay_load_harvest), their Grp reduced from the same words (mj_harvest_grp).  Returns a list per game
+        of Gameplay, one per wanted seat; the list of a game that ended in error is empty.  seats / names as load_pool.
+        oracle=True deals every wall from the seed recorded with the game.  augmented=True is refused like in load_pool."""
+        harvest._handle()  # (a closed Harvest is refused before anything else)
+        return self._load_device("load_harvest", "games", "harvest", harvest.n_games, game0, n_games, seats, names, harvest.pool_cls,
+                                 harvest, harvest.grp, lambda rp, first, tracked: rp.replay_load_harvest(
+                                     harvest, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle))
+
+    def _load_device(self, who, unit, where, n_src, first, count, seats, names, pool_cls, src, grp_of, load_into):
+        """load_pool / load_harvest: logs [first, first + count) of a device source (`src`: device, deal_algo, log_cap) -> the
+        Gameplays.  grp_of(first, n) -> the Grps (None = skipped), load_into(replay pool, first, tracked) loads the scripts."""
         if self.augmented:
-            raise ValueError("load_pool: augmented=True is not supported (the arena's device log is not suit-swapped and this "
+            raise ValueError(f"{who}: augmented=True is not supported (the arena's device log is not suit-swapped and this "
                              "route has no host encoder to swap it): dump the logs and use load_logs / load_gz_log_files")
-        n = pool.n_tables - table0 if n_tables is None else int(n_tables)
-        if table0 < 0 or n < 0 or table0 + n > pool.n_tables:
-            raise ValueError(f"load_pool: tables [{table0}, {table0 + n}) are not in a pool of {pool.n_tables}")
+        n = n_src - first if count is None else int(count)
+        if first < 0 or n < 0 or first + n > n_src:
+            raise ValueError(f"{who}: {unit} [{first}, {first + n}) are not in a {where} of {n_src}")
         if n == 0:
             return []
         masks = np.full(n, 15, dtype=np.uint8) if seats is None else np.ascontiguousarray(seats, dtype=np.uint8)
@@ -413,18 +431,18 @@ class GameplayLoader:
             raise ValueError(f"seats: expected {n} masks, got shape {masks.shape}")
         if names is not None and len(names) != n:
             raise ValueError(f"names: expected {n} lists of four names, got {len(names)}")
-        grps = pool.log_grp(table0, n)
+        grps = grp_of(first, n)
         games = []
         for t in range(n):
             nm = list(names[t]) if names is not None else ["", "", "", ""]
             wanted = [p for p in (self._wanted(nm) if names is not None else range(4)) if (int(masks[t]) >> p) & 1]
             games.append(dict(names=nm, wanted=wanted if grps[t] is not None else [], grp=grps[t]))
         tracked = [sum(1 << p for p in g["wanted"]) for g in games]
-        rp = type(pool)(n, version=self.version, device=str(pool.device), max_rows=8 * n + 64, deal_algo=pool.deal_algo)
+        rp = pool_cls(n, version=self.version, device=str(src.device), max_rows=8 * n + 64, deal_algo=src.deal_algo)
         try:
-            rp.replay_load_pool(pool, table0, tracked, self.always_include_kan_select, deal_from_seed=self.oracle)
+            load_into(rp, first, tracked)
             # every step applies at least one event of every unfinished log, and an event takes at least one word
-            samples = self._replay_samples(rp, n, pool.log_cap + 8, table0)
+            samples = self._replay_samples(rp, n, src.log_cap + 8, first)
         finally:
             rp.close()
         return self._slice_gameplays(games, *samples)

@@ -45,6 +45,98 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# include/mortal_amd.h MjHarvestGame
+HARVEST_GAME_DTYPE = np.dtype([("seed_nonce", "<u8"), ("seed_key", "<u8"), ("first_word", "<u8"), ("n_words", "<u4"),
+                               ("game_id", "<u4"), ("table", "<u4"), ("cycle", "<u4"), ("scores", "<i4", (4,)), ("err", "u1"),
+                               ("agent_of_seat", "u1"), ("reserved", "u1", (6,))])
+assert HARVEST_GAME_DTYPE.itemsize == 64
+
+
+class Harvest:
+    """The finished games a pool in refill mode has collected (TablePool.take_harvest): what the reference's arena returns as
+    a list of GameResult (arena/game.rs:291-296, arena/result.rs:19-51), kept on the device.  It owns its device memory and is
+    independent of the pool from then on: later steps and later takes do not change it.
+
+    n_games / n_words / dropped (games that found the buffer full while it was the pool's active one) / n_errors;
+    games: structured array of the records (HARVEST_GAME_DTYPE), sorted by (game_id, table) -- "game i" is row i."""
+
+    def __init__(self, pool, handle):
+        self._L = pool._L
+        self._stream = pool._stream
+        self.pool_cls = type(pool)
+        self.device = pool.device
+        self.deal_algo = pool.deal_algo
+        self.log_cap = pool.log_cap
+        self.h = handle
+        info = np.zeros(4, dtype=np.int64)
+        pool._check(self._L.mj_harvest_info(self.h, info.ctypes.data))
+        self.n_games, self.n_words, self.dropped, self.n_errors = (int(x) for x in info)
+        self.games = np.zeros(self.n_games, dtype=HARVEST_GAME_DTYPE)
+        pool._check(self._L.mj_harvest_games(self.h, self.games.ctypes.data if self.n_games else None))
+
+    def __len__(self):
+        return self.n_games
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.mj_harvest_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise MortalAmdError("the Harvest is closed")
+        return self.h
+
+    def _fail(self):
+        return MortalAmdError(self._L.mj_last_error().decode())
+
+    def read_logs(self):
+        """-> list (one per game) of uint64 arrays: the event words of the game, as TablePool.read_logs returned them for its
+        table before the restart (empty for a game in error)."""
+        h = self._handle()
+        out = []
+        for i in range(self.n_games):
+            buf = np.empty(int(self.games["n_words"][i]), dtype=np.uint64)
+            if self._L.mj_harvest_read(h, i, buf.ctypes.data if len(buf) else None) < 0:
+                raise self._fail()
+            out.append(buf)
+        return out
+
+    def stat(self, seats=None, per_seat=False):
+        """libriichi's Stat of the collected games, reduced on the device (mj_harvest_stat) -> what TablePool.log_stat returns:
+        (totals [Stat of agent 0's seats, Stat of agent 1's seats], per-seat int64 [n_games, 4, 44] or None, counts); a game in
+        error is skipped."""
+        from .stat import _stat_call
+
+        h = self._handle()
+
+        def call(p_seats, p_totals, p_rows, p_counts):
+            if self._L.mj_harvest_stat(h, p_seats, p_totals, p_rows, p_counts, self._stream()) < 0:
+                raise self._fail()
+
+        return _stat_call(call, self.n_games, seats, per_seat)
+
+    def grp(self, game0=0, n=None, max_kyoku=64):
+        """dataset/grp.rs `Grp` of games [game0, game0 + n) (n None = to the last), reduced on the device (mj_harvest_grp), as
+        TablePool.log_grp: None for a game in error, ValueError for a malformed log."""
+        from .dataset import _grp_call
+
+        h = self._handle()
+        n = self.n_games - game0 if n is None else int(n)
+
+        def call(*ptrs):
+            if self._L.mj_harvest_grp(h, int(game0), n, int(max_kyoku), *ptrs, self._stream()) < 0:
+                raise self._fail()
+
+        grps, n_kyoku, _counts = _grp_call(call, max(n, 0), max_kyoku)
+        bad = np.flatnonzero(n_kyoku < 0)
+        if len(bad):
+            raise ValueError(f"game {game0 + int(bad[0])}: malformed event log (or more than {max_kyoku} kyoku)")
+        return grps
+
+
 class TablePool:
     _L = lib  # the C-ABI library (tests/host/emu_pool.py substitutes the host emulation of the same sources)
 
@@ -183,6 +275,24 @@ class TablePool:
         self.n_rows = [0, 0]
         return dict(loaded=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2]))
 
+    def replay_load_harvest(self, harvest, game0=0, tracked=None, always_include_kan_select=True, deal_from_seed=False):
+        """The same from a Harvest: games [game0, game0 + self.n_tables) of its sorted order (mj_replay_load_harvest); the seeds
+        come from the records.  -> dict(loaded, skipped, malformed): a game in error is skipped."""
+        tr = None
+        if tracked is not None:
+            tr = np.ascontiguousarray(tracked, dtype=np.uint8)
+            if tr.shape != (self.n_tables,):
+                raise ValueError(f"tracked: expected {self.n_tables} masks, got shape {tr.shape}")
+        if not isinstance(harvest, Harvest) or harvest._L is not self._L:
+            raise MortalAmdError("replay_load_harvest: the source must be a Harvest of the same library")
+        counts = np.zeros(3, dtype=np.int64)
+        if self._L.mj_replay_load_harvest(self.h, harvest._handle(), int(game0), tr.ctypes.data if tr is not None else None,
+                                          int(always_include_kan_select), int(deal_from_seed), counts.ctypes.data,
+                                          self._stream()) < 0:
+            raise MortalAmdError(self._L.mj_last_error().decode())
+        self.n_rows = [0, 0]
+        return dict(loaded=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2]))
+
     def replay_step(self):
         check(self._L.mj_replay_step(self.h, self._stream()))
         out = (C.c_int32 * 2)()
@@ -204,6 +314,31 @@ class TablePool:
     def set_start_stagger(self, cycles):
         """Steady-state runs: table t starts its first hanchan at cycle hash(t) % cycles (after reset + set_refill)."""
         check(self._L.mj_pool_set_start_stagger(self.h, int(cycles), self._stream()))
+
+    # ---- finished games of a pool in refill mode (include/mortal_amd.h mj_pool_enable_harvest ..)
+    def _check(self, rc):
+        if rc < 0:
+            raise MortalAmdError(self._L.mj_last_error().decode())  # (the error text of the library this pool runs on)
+        return rc
+
+    def enable_harvest(self, max_games, max_words):
+        """Collect every finished game on the device just before its table is restarted (needs enable_log; collects while
+        set_refill is on): room for max_games games and max_words log words.  A game that finds the buffer full is dropped
+        and counted.  Calling it again replaces the buffer and discards what it held; max_games 0 turns harvesting off."""
+        self._check(self._L.mj_pool_enable_harvest(self.h, int(max_games), int(max_words)))
+
+    def harvest_pending(self):
+        """-> dict(games, words, dropped) in the active buffer right now."""
+        out = np.zeros(3, dtype=np.int64)
+        self._check(self._L.mj_harvest_pending(self.h, out.ctypes.data, self._stream()))
+        return dict(games=int(out[0]), words=int(out[1]), dropped=int(out[2]))
+
+    def take_harvest(self):
+        """Detach what has been collected as a Harvest; the pool goes on collecting into a fresh buffer.  A game that has
+        finished but whose table has not been restarted yet (that happens in the next step) is in the next take."""
+        hp = C.c_void_p()
+        self._check(self._L.mj_harvest_take(self.h, C.byref(hp), self._stream()))
+        return Harvest(self, hp)
 
     def step(self, actions0=None, actions1=None, q0=None, q1=None, ev0=None, ev1=None):
         """One arena cycle; actionsN = int32 cuda tensor with one action per row of agent N's last batch; qN = that
