@@ -28,6 +28,7 @@
  *   mj_replay_load_pool   arena/result.rs:32-51 dump_json_log -> dataset/gameplay.rs:66-124 load_gz_log_files (the log files between
  *                         self-play and the loader), without the files: the arena's device log is the loader's script
  *   mj_pool_grp, mj_grp_logs     dataset/grp.rs:90-164 Grp::load_events
+ *   MJ_LOAD_AUGMENT, mj_augment_logs   dataset/gameplay.rs:126-128 (augmented) -> mjai/event.rs:187-217 Event::augment, tile.rs:154-167
  *   mj_pool_enable_harvest, mj_harvest_pending, mj_harvest_take, mj_harvest_info / _games / _read / _destroy
  *                         arena/game.rs:291-296 (a finished game's GameResult is handed over while the others play on) +
  *                         arena/result.rs:19-51 (what a GameResult keeps: seed, scores, log)
@@ -123,12 +124,20 @@ int mj_replay_load(MjPool* pool, const uint64_t* script_host, const uint32_t* of
  * dst->n_tables tables, copied on the device.  A table whose game has not finished without an error (done != 1) gets an empty
  * script and is counted as skipped; one whose log_len exceeds the log's capacity or whose event chain runs past its end or meets an
  * unknown event type is counted as malformed and gets an empty script too.  counts_out = {loaded, skipped, malformed}.
- * tracked_host: [dst n_tables] seat masks, NULL = all four seats.  deal_from_seed: every start_kyoku asks for the wall to be rebuilt
- * from the seed (LG_SK_DEAL_BIT) and dst's table t takes the seed of src's table table0 + t.  Needs mj_pool_enable_log on src;
+ * tracked_host: [dst n_tables] seat masks, NULL = all four seats.  flags: MJ_LOAD_* below, 0 and 1 mean what the former
+ * `int deal_from_seed` meant; any other bit is an error that leaves dst as it was.  MJ_LOAD_DEAL_FROM_SEED: every start_kyoku asks for
+ * the wall to be rebuilt from the seed (LG_SK_DEAL_BIT) and dst's table t takes the seed of src's table table0 + t.  MJ_LOAD_AUGMENT:
+ * the copy swaps manzu and pinzu in every tile field of the script (GameplayLoader(augmented=True), dataset/gameplay.rs:126-128:
+ * Event::augment of every event -- dora marker and haipai of start_kyoku, pai / consumed of tsumo, dahai, dora, chi, pon, the three
+ * kans, ura markers of hora; kyoku number, winds, scores, deltas and tag words stay); with both flags every start_kyoku also carries
+ * LG_SK_AUG_BIT: the wall is dealt from the seed as it was and compared with the script through the swap (the reference's mix of
+ * swapped events and an unswapped Invisible).  src's log is never changed.  Needs mj_pool_enable_log on src;
  * an error if src is in refill mode (a restarted table's log has been rewound; mj_replay_load_harvest is the route there), if src == dst or if the range leaves src.  Ordered
  * behind the steps of src already launched; synchronous; src is never modified.  Afterwards dst is where mj_replay_load leaves it. */
+#define MJ_LOAD_DEAL_FROM_SEED 1
+#define MJ_LOAD_AUGMENT 2
 int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tracked_host /* NULL ok */,
-                        int always_include_kan_select, int deal_from_seed, int64_t counts_out[3], void* stream);
+                        int always_include_kan_select, int flags /* MJ_LOAD_* */, int64_t counts_out[3], void* stream);
 int mj_replay_step(MjPool* pool, void* stream);
 int mj_replay_meta(MjPool* pool, int32_t* meta_dev, void* stream);
 
@@ -246,6 +255,12 @@ int mj_grp_logs(const uint64_t* words_host, const uint32_t* off_host /* [n_logs 
  * route there); ordered behind the steps already launched; synchronous. */
 int mj_pool_grp(MjPool* pool, int table0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
                 int32_t* final_out, int64_t counts_out[3], void* stream);
+/* Event::augment (mjai/event.rs:187-217) of packed host logs, through the copy kernel of mj_replay_load_pool with MJ_LOAD_AUGMENT and
+ * back: addressing as mj_grp_logs, words_out_host as large as words_host (it may be words_host itself).  A log whose chain is a
+ * sequence of known events that ends at its end is written, swapped, to its own offsets; a malformed one is copied unchanged.
+ * counts_out = {logs done, empty, malformed}.  No header bit is set or cleared, so the call is its own inverse.  Synchronous. */
+int mj_augment_logs(const uint64_t* words_host, const uint32_t* off_host /* [n_logs + 1] */, int n_logs,
+                    uint64_t* words_out_host /* as words_host */, int64_t counts_out[3] /* done / empty / malformed */, void* stream);
 
 /* ---- Finished games of a pool in refill mode (kernel: mortal_amd/csrc/mj_harvest.hip).  The reference's arena hands each GameResult
  * over as its game finishes (arena/game.rs:291-296) and a GameResult keeps seed, scores and log (arena/result.rs:19-51).  Here a
@@ -290,11 +305,12 @@ int mj_harvest_stat(const MjHarvest* h, const uint8_t* seats_host, int64_t* tota
 /* mj_pool_grp over games [game0, game0 + n) of the harvest. */
 int mj_harvest_grp(const MjHarvest* h, int game0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
                    int32_t* final_out, int64_t counts_out[3], void* stream);
-/* mj_replay_load_pool from a harvest: log t of `dst` = game game0 + t, for all dst->n_tables tables; with deal_from_seed the seeds come
+/* mj_replay_load_pool from a harvest: log t of `dst` = game game0 + t, for all dst->n_tables tables; flags = MJ_LOAD_* as there
+ * (MJ_LOAD_AUGMENT: the script is suit-swapped on the way; an unknown bit is an error), with MJ_LOAD_DEAL_FROM_SEED the seeds come
  * from the records.  A game in error is skipped.  The destination is built beside dst and moved in last: a failing call leaves dst
  * and the harvest as they were. */
 int mj_replay_load_harvest(MjPool* dst, const MjHarvest* h, int game0, const uint8_t* tracked_host /* NULL ok */,
-                           int always_include_kan_select, int deal_from_seed, int64_t counts_out[3], void* stream);
+                           int always_include_kan_select, int flags /* MJ_LOAD_* */, int64_t counts_out[3], void* stream);
 
 /* First table in error: returns its error code (>0) and index, or 0. */
 int mj_pool_first_error(MjPool* pool, int* table_out, void* stream);

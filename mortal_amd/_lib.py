@@ -14,7 +14,7 @@ SYMBOLS = [
     "mj_pool_configure", "mj_pool_set_refill", "mj_pool_set_start_stagger", "mj_table_apply_event", "mj_table_mark_row", "mj_table_query", "mj_replay_load", "mj_replay_step", "mj_replay_meta", "mj_pool_enable_log", "mj_log_lengths", "mj_log_read", "mj_step", "mj_step_q", "mj_step_ev", "mj_rows_count", "mj_rows_dev", "mj_encode",
     "mj_encode_oracle", "mj_oracle_obs_rows", "mj_encode_timing", "mj_sp_timing", "mj_sp_phase_ticks", "mj_pool_set_sp_schedule", "mj_sp_schedule_stats", "mj_random_policy", "mj_greedy_policy", "mj_counters", "mj_results", "mj_pool_first_error", "mj_debug_table",
     "mj_debug_table_size", "mj_debug_layout", "mj_obs_rows", "mj_algo_query", "mj_stat_logs", "mj_pool_stat",
-    "mj_replay_load_pool", "mj_grp_logs", "mj_pool_grp",
+    "mj_replay_load_pool", "mj_grp_logs", "mj_pool_grp", "mj_augment_logs",
     "mj_pool_enable_harvest", "mj_harvest_pending", "mj_harvest_take", "mj_harvest_destroy", "mj_harvest_info", "mj_harvest_games",
     "mj_harvest_read", "mj_harvest_stat", "mj_harvest_grp", "mj_replay_load_harvest",
 ]
@@ -87,6 +87,7 @@ def _load(path=None):
     L.mj_replay_load_pool.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
     L.mj_grp_logs.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.mj_pool_grp.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.mj_augment_logs.argtypes = [vp, vp, i32, vp, vp, vp]
     L.mj_pool_enable_harvest.argtypes = [vp, C.c_uint32, u64]
     L.mj_harvest_pending.argtypes = [vp, vp, vp]
     L.mj_harvest_take.argtypes = [vp, vp, vp]

@@ -369,17 +369,18 @@ class BatchRunner(_EngineRunner):
         name are summed there too, stat.rs:443-498)."""
         return _stats_by_name([c["name"] for c in self.cfg], [t.counters() for t in self.agent_stats()])
 
-    def gameplays(self, loader, seats=None):
+    def gameplays(self, loader, seats=None, augmented=False):
         """After run(): the training samples of every game, replayed from the device log without a file in between
         (GameplayLoader.load_pool; keep_log / keep_stat, anything that enabled the device log) -> a list per game of Gameplay,
-        one per wanted seat, named like the dumped logs name the seats (game.rs:186).  seats: 4-bit seat mask per game."""
+        one per wanted seat, named like the dumped logs name the seats (game.rs:186).  seats: 4-bit seat mask per game;
+        augmented: the suit-swapped second pass of the reference's data loader (GameplayLoader.load_pool)."""
         if not getattr(self.pool, "log_cap", 0):
             raise MortalAmdError("gameplays: the device log is off (create the runner with keep_log or keep_stat)")
         names_of_agent = [c["name"] for c in self.cfg]
         if len(names_of_agent) == 1:
             names_of_agent = names_of_agent * 2
         names = [[names_of_agent[(int(self.agent_of_seat[g]) >> s) & 1] for s in range(4)] for g in range(self.pool.n_tables)]
-        return loader.load_pool(self.pool, seats=seats, names=names)
+        return loader.load_pool(self.pool, seats=seats, names=names, augmented=augmented)
 
     @staticmethod
     def _meta(batch, row, tag, with_batch=False):
@@ -501,10 +502,11 @@ class SelfPlayRunner(_EngineRunner):
             names_of_agent = names_of_agent * 2
         return [[names_of_agent[(int(m) >> s) & 1] for s in range(4)] for m in harvest.games["agent_of_seat"]]
 
-    def gameplays(self, loader, harvest, seats=None):
+    def gameplays(self, loader, harvest, seats=None, augmented=False):
         """The training samples of every game of the harvest (GameplayLoader.load_harvest) -> a list per game of Gameplay, one per
-        wanted seat, the seats named by engine as BatchRunner.gameplays names them.  seats: 4-bit seat mask per game."""
-        return loader.load_harvest(harvest, seats=seats, names=self._names(harvest))
+        wanted seat, the seats named by engine as BatchRunner.gameplays names them.  seats: 4-bit seat mask per game; augmented:
+        the suit-swapped form of the same games."""
+        return loader.load_harvest(harvest, seats=seats, names=self._names(harvest), augmented=augmented)
 
     def stats(self, harvest):
         """{engine name: Stat} over the games of the harvest (games in error are left out)."""

@@ -1295,7 +1295,10 @@ struct SeedSrc {
 // Everything is built beside the destination and moved in last: its tables and counters too, so that no failure -- the last
 // synchronise included -- can leave it between two scripts.
 int replay_load_src(const std::string& who, MjPool* dst, const LogSrc& S, const SeedSrc& seeds, const uint8_t* tracked_host,
-                    int always_include_kan_select, int deal_from_seed, int64_t counts_out[3], hipStream_t s) {
+                    int always_include_kan_select, int flags, int64_t counts_out[3], hipStream_t s) {
+    if (flags & ~(MJ_LOAD_DEAL_FROM_SEED | MJ_LOAD_AUGMENT))
+        return fail(who + ": unknown load flags " + std::to_string(flags) + " (MJ_LOAD_DEAL_FROM_SEED | MJ_LOAD_AUGMENT)");
+    const int deal_from_seed = flags & MJ_LOAD_DEAL_FROM_SEED;
     const int n = dst->n_tables;
     ReplayBufs R;
     DevBuf<TableBlock> blocks;
@@ -1328,7 +1331,8 @@ int replay_load_src(const std::string& who, MjPool* dst, const LogSrc& S, const 
         return fail(who + ": " + std::to_string(sums_host[3]) + " script words do not fit the 32-bit offsets: load fewer tables per call");
     if (R.script.alloc((size_t)sums_host[3] + 1)) return -1;
     const LogPackParams pp = {S, R.off.get(), R.script.get(), deal_from_seed};
-    hipLaunchKernelGGL(mj_k_log_pack, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
+    if (flags & MJ_LOAD_AUGMENT) hipLaunchKernelGGL(mj_k_log_pack<true>, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
+    else hipLaunchKernelGGL(mj_k_log_pack<false>, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(s));
     for (int k = 0; k < 3; k++) counts_out[k] = (int64_t)sums_host[k];
@@ -1343,7 +1347,7 @@ int replay_load_src(const std::string& who, MjPool* dst, const LogSrc& S, const 
 }  // namespace
 
 int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tracked_host, int always_include_kan_select,
-                        int deal_from_seed, int64_t counts_out[3], void* stream) {
+                        int flags, int64_t counts_out[3], void* stream) {
     if (!dst || !src) return fail("null pool");
     if (!counts_out) return fail("mj_replay_load_pool: null counts buffer");
     memset(counts_out, 0, 3 * sizeof(int64_t));
@@ -1356,7 +1360,55 @@ int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tra
     hipStream_t s = (hipStream_t)stream;
     if (src->ev_snap && s != src->step_stream) HIP_OK(hipStreamWaitEvent(s, src->ev_snap.get(), 0));  // behind the source's last step
     return replay_load_src("mj_replay_load_pool", dst, pool_log_src(src, table0, n), SeedSrc{src->blocks.get(), table0, nullptr, nullptr},
-                           tracked_host, always_include_kan_select, deal_from_seed, counts_out, s);
+                           tracked_host, always_include_kan_select, flags, counts_out, s);
+}
+
+// Packed host logs through the augmenting copy and back (the pack walk of the loads above, over concatenated logs).  The three
+// passes compact the accepted logs; the host puts each back at its own offsets, a malformed one stays as it came.
+int mj_augment_logs(const uint64_t* words_host, const uint32_t* off_host, int n_logs, uint64_t* words_out_host, int64_t counts_out[3],
+                    void* stream) {
+    if (!counts_out) return fail("mj_augment_logs: null counts buffer");
+    memset(counts_out, 0, 3 * sizeof(int64_t));
+    if (n_logs <= 0) return n_logs < 0 ? fail("mj_augment_logs: negative n_logs") : 0;
+    if (!off_host) return fail("mj_augment_logs: null offsets");
+    for (int i = 0; i < n_logs; i++)  // the kernel trusts the offsets: a log lies inside [0, off[n_logs])
+        if (off_host[i] > off_host[i + 1]) return fail("mj_augment_logs: offsets of log " + std::to_string(i) + " decrease");
+    const size_t n_words = off_host[n_logs], n = (size_t)n_logs;
+    if (n_words && (!words_host || !words_out_host)) return fail("mj_augment_logs: null words");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf<uint64_t> b_words, b_out;
+    DevBuf<uint32_t> b_off, b_len, b_pack;  // b_pack: the compacted offsets [n + 1]
+    DevBuf<unsigned long long> b_sums;      // done / empty / malformed, total words
+    if (stat_upload(b_words, words_host, n_words, s) || stat_upload(b_off, off_host, n + 1, s) || b_out.alloc(n_words + 1) ||
+        b_len.alloc(n) || b_pack.alloc(n + 1) || b_sums.alloc(4))
+        return -1;
+    HIP_OK(hipMemsetAsync(b_sums.get(), 0, 4 * sizeof(unsigned long long), s));
+    LogSrc S{};
+    S.words = b_words.get();
+    S.off = b_off.get();
+    S.n_logs = n_logs;
+    const int grid = log_grid(n);
+    const LogLenParams lp = {S, b_len.get(), b_sums.get()};
+    hipLaunchKernelGGL(mj_k_log_len, dim3(grid), dim3(LOGK_THREADS), 0, s, lp);
+    hipLaunchKernelGGL(mj_k_log_scan, dim3(1), dim3(1024), 0, s, b_len.get(), n_logs, b_pack.get(), b_sums.get() + 3);
+    const LogPackParams pp = {S, b_pack.get(), b_out.get(), 0};
+    hipLaunchKernelGGL(mj_k_log_pack<true>, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
+    HIP_OK(hipGetLastError());
+    std::vector<uint32_t> len(n);
+    std::vector<uint64_t> packed(n_words);
+    unsigned long long sums_host[4];
+    HIP_OK(hipMemcpyAsync(len.data(), b_len.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (n_words) HIP_OK(hipMemcpyAsync(packed.data(), b_out.get(), n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(sums_host, b_sums.get(), sizeof sums_host, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    size_t at = 0;  // (an accepted log's length is its own, so the compacted words never outrun n_words)
+    for (size_t i = 0; i < n; i++) {
+        const size_t lo = off_host[i], k = off_host[i + 1] - lo;
+        if (len[i] == k && k) memcpy(words_out_host + lo, packed.data() + at, k * sizeof(uint64_t)), at += k;
+        else if (k) memmove(words_out_host + lo, words_host + lo, k * sizeof(uint64_t));
+    }
+    for (int k = 0; k < 3; k++) counts_out[k] = (int64_t)sums_host[k];
+    return 0;
 }
 
 // ---------------------------------------------------------------- finished games of a refilling pool (mj_harvest.hip)
@@ -1494,7 +1546,7 @@ int mj_harvest_grp(const MjHarvest* h, int game0, int n, int max_kyoku, int32_t*
 }
 
 int mj_replay_load_harvest(MjPool* dst, const MjHarvest* h, int game0, const uint8_t* tracked_host, int always_include_kan_select,
-                           int deal_from_seed, int64_t counts_out[3], void* stream) {
+                           int flags, int64_t counts_out[3], void* stream) {
     if (!dst || !h) return fail("null pool / harvest");
     if (!counts_out) return fail("mj_replay_load_harvest: null counts buffer");
     memset(counts_out, 0, 3 * sizeof(int64_t));
@@ -1502,7 +1554,7 @@ int mj_replay_load_harvest(MjPool* dst, const MjHarvest* h, int game0, const uin
     if (game0 < 0 || game0 > (int)h->games.size() - n) return fail("mj_replay_load_harvest: game range out of bounds");
     return replay_load_src("mj_replay_load_harvest", dst, harvest_log_src(h, game0, n),
                            SeedSrc{nullptr, 0, h->nonce.get() + game0, h->key.get() + game0}, tracked_host, always_include_kan_select,
-                           deal_from_seed, counts_out, (hipStream_t)stream);
+                           flags, counts_out, (hipStream_t)stream);
 }
 
 __global__ void mj_k_first_error(const TableBlock* blocks, int n_tables, unsigned long long* out) {

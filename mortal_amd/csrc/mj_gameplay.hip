@@ -64,15 +64,82 @@ MJD int log_event_len(uint32_t w_lo, uint32_t w_hi) {  // mj_replay.hip rp_len
     return (t == LG_HORA ? 4 : t == LG_RYUKYOKU ? 3 : 1) + (int)((w_hi >> (LG_TAG_BIT - 32)) & 1);
 }
 
+// ---- suit augmentation on the way through (the reference's GameplayLoader(augmented=True): mjai/event.rs:187-217 Event::augment,
+// tile.rs:154-167 Tile::augment).  What a word is -- a header, haipai tiles, wall tiles, ura indicators, or a tag / score / delta
+// word that only looks like one of them -- is known from the walk alone, so the walk hands every window a few lane masks and each
+// lane rewrites its own word by the mask it is in.  An event can straddle a window boundary: the walk keeps the last header it
+// followed (position and both halves, wave-uniform) and enters that event's roles again in the window its payload runs into.
+MJD uint32_t log_aug_tile(uint32_t t) {  // manzu <-> pinzu, 5mr <-> 5pr; ids >= 36 and the honours stay
+    return t < 9 ? t + 9 : t < 18 ? t - 9 : t == 34 ? 35u : t == 35 ? 34u : t;
+}
+struct LogRoles {          // one bit per lane of the window
+    uint64_t hdr;          // an event header: 6-bit tile fields chosen by its own type
+    uint64_t bytes8;       // haipai words 1..6 and the 17 wall words: 8 tile bytes
+    uint64_t bytes4;       // the 7th haipai word: tile bytes 0..3 (the upper four are unused and stay 0)
+    uint64_t ura0, ura1, ura2;  // a hora's ura word: the bit planes of the header's n_ura (that many 6-bit fields from bit 0)
+};
+MJD uint64_t log_win_mask(uint32_t lo, uint32_t hi, uint32_t base) {  // words [lo, hi) of the log as lanes of the window at `base`
+    const uint32_t a = max(lo, base), b = min(hi, base + 64u);
+    if (a >= b) return 0ull;
+    return (b - a == 64u ? ~0ull : (1ull << (b - a)) - 1) << (a - base);
+}
+// the payload roles of the event whose header (w_lo, w_hi) stands at word p, as far as they fall into the window; wave-uniform
+MJD void log_roles_add(LogRoles& R, uint32_t p, uint32_t w_lo, uint32_t w_hi, uint32_t base) {
+    const int t = w_lo & 15;
+    if (t == LG_START_KYOKU) {
+        R.bytes8 |= log_win_mask(p + 3, p + 9, base);
+        R.bytes4 |= log_win_mask(p + 9, p + 10, base);
+        if ((w_hi >> (LG_SK_WALL_BIT - 32)) & 1) R.bytes8 |= log_win_mask(p + 10, p + 27, base);
+    } else if (t == LG_HORA) {
+        const uint32_t u = p + 3 + ((w_hi >> (LG_TAG_BIT - 32)) & 1), n = (w_hi >> (LG_NURA_SHIFT - 32)) & 7;
+        const uint64_t m = log_win_mask(u, u + 1, base);
+        R.ura0 |= n & 1 ? m : 0ull, R.ura1 |= n & 2 ? m : 0ull, R.ura2 |= n & 4 ? m : 0ull;
+    }
+}
+// a lane's own word through the swap; `deal`: a start_kyoku header also takes LG_SK_DEAL_BIT and LG_SK_AUG_BIT
+MJD uint64_t log_aug_word(uint64_t w, const LogRoles& R, int lane, bool deal) {
+    uint32_t fields = 0, width = 6, shift = 0;  // bit k of `fields`: the tile at bit shift + k * width
+    if ((R.hdr >> lane) & 1) {
+        const int t = (int)(w & 15);
+        shift = 8;  // pai, c0, c1, c2, c3 (LG_WORD); a start_kyoku's c0 is the kyoku number, a hora header holds no tile
+        fields = t == LG_START_KYOKU || t == LG_TSUMO || t == LG_DAHAI || t == LG_DORA ? 1u
+                 : t == LG_CHI || t == LG_PON                                          ? 7u
+                 : t == LG_DAIMINKAN || t == LG_KAKAN                                  ? 15u
+                 : t == LG_ANKAN                                                       ? 30u
+                                                                                       : 0u;
+        if (deal && t == LG_START_KYOKU) w |= (1ull << LG_SK_DEAL_BIT) | (1ull << LG_SK_AUG_BIT);
+    } else if ((R.bytes8 >> lane) & 1) {
+        fields = 0xFFu, width = 8;
+    } else if ((R.bytes4 >> lane) & 1) {
+        fields = 0x0Fu, width = 8;
+    } else {
+        const uint32_t n = (uint32_t)((R.ura0 >> lane) & 1) | (uint32_t)((R.ura1 >> lane) & 1) << 1 | (uint32_t)((R.ura2 >> lane) & 1) << 2;
+        fields = (1u << n) - 1;
+    }
+    const uint64_t in = w;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) {
+        const uint32_t sh = shift + k * width, t = (uint32_t)(in >> sh) & ((1u << width) - 1);
+        if ((fields >> k) & 1) w ^= (uint64_t)(t ^ log_aug_tile(t)) << sh;
+    }
+    return w;
+}
+
 // Walks the chain of one log in fixed 64-word windows.  `store`: NULL, or where the words go; `deal_bit`: set LG_SK_DEAL_BIT in
 // every start_kyoku header on the way.  -> the chain is a sequence of known events that ends exactly at `len`.
+// AUG: the stored words are suit-augmented (above), and `deal_bit` sets LG_SK_AUG_BIT as well; the plain walk is what it was.
+template <bool AUG>
 MJD bool log_walk(const uint64_t* lw, uint32_t len, int lane, uint64_t* store, bool deal_bit) {
     uint32_t pos = 0;  // wave-uniform: the next header
     bool bad = false;
+    uint32_t ev_pos = 0, ev_lo = 0, ev_hi = 0;  // AUG, wave-uniform: the last header followed
     for (uint32_t base = 0; base < len; base += 64) {
         const uint64_t mine = base + (uint32_t)lane < len ? lw[base + lane] : 0ull;  // never beyond len
         const uint32_t end = min(base + 64u, len);
         uint64_t sk = 0;  // window lanes that hold a start_kyoku header
+        LogRoles R{};
+        if constexpr (AUG)
+            if (pos > base) log_roles_add(R, ev_pos, ev_lo, ev_hi, base);  // the payload the previous window left behind
         while (pos < end && !bad) {
             const int k = __builtin_amdgcn_readfirstlane((int)(pos - base));
             const uint64_t wv = __shfl(mine, k);
@@ -81,10 +148,19 @@ MJD bool log_walk(const uint64_t* lw, uint32_t len, int lane, uint64_t* store, b
             const int t = w_lo & 15;
             if (t < LG_START_KYOKU || t > LG_END_KYOKU) bad = true;
             if (t == LG_START_KYOKU) sk |= 1ull << k;
+            if constexpr (AUG) {
+                R.hdr |= 1ull << k;
+                log_roles_add(R, pos, w_lo, w_hi, base);
+                ev_pos = pos, ev_lo = w_lo, ev_hi = w_hi;
+            }
             pos += (uint32_t)log_event_len(w_lo, w_hi);
         }
-        if (store && base + (uint32_t)lane < len)
-            store[base + lane] = mine | (deal_bit && ((sk >> lane) & 1) ? 1ull << LG_SK_DEAL_BIT : 0ull);
+        if constexpr (AUG) {
+            if (store && base + (uint32_t)lane < len) store[base + lane] = log_aug_word(mine, R, lane, deal_bit);
+        } else {
+            if (store && base + (uint32_t)lane < len)
+                store[base + lane] = mine | (deal_bit && ((sk >> lane) & 1) ? 1ull << LG_SK_DEAL_BIT : 0ull);
+        }
         if (bad && !store) break;
     }
     return !bad && pos == len;
@@ -103,7 +179,7 @@ __global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_len(LogLenParams P) {
         const uint64_t* lw;
         uint32_t len;
         int st = log_locate(P.src, i, lw, len);
-        if (st == LOG_OK && !log_walk(lw, len, lane, nullptr, false)) st = LOG_BAD;
+        if (st == LOG_OK && !log_walk<false>(lw, len, lane, nullptr, false)) st = LOG_BAD;
         if (lane == 0) P.len_out[i] = st == LOG_OK ? len : 0u;
         n_ok += st == LOG_OK, n_skip += st == LOG_SKIP, n_bad += st == LOG_BAD;
     }
@@ -148,6 +224,9 @@ struct LogPackParams {
     uint64_t* script;
     int deal_from_seed;
 };
+// AUG: the words go through the suit swap (log_walk<true>); the plain instantiation is the copy it was
+
+template <bool AUG>
 __global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_pack(LogPackParams P) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int i = blockIdx.x * LOGK_WAVES + wave; i < P.src.n_logs; i += gridDim.x * LOGK_WAVES) {
@@ -157,8 +236,10 @@ __global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_pack(LogPackParams P) {
         uint32_t len;
         log_locate(P.src, i, lw, len);  // (n == len: pass 1 accepted this log)
         uint64_t* out = P.script + (size_t)P.off[i];
-        if (P.deal_from_seed) {
-            log_walk(lw, n, lane, out, true);
+        if constexpr (AUG) {
+            log_walk<true>(lw, n, lane, out, P.deal_from_seed != 0);
+        } else if (P.deal_from_seed) {
+            log_walk<false>(lw, n, lane, out, true);
         } else {
             for (uint32_t k = lane; k < n; k += 64) out[k] = lw[k];
         }

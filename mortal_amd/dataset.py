@@ -386,7 +386,7 @@ class GameplayLoader:
             pool.close()
         return self._slice_gameplays(games, *samples)
 
-    def load_pool(self, pool, table0=0, n_tables=None, seats=None, names=None):
+    def load_pool(self, pool, table0=0, n_tables=None, seats=None, names=None, augmented=False):
         """The samples of a pool's finished games straight from its device log (TablePool.enable_log), without JSON or files:
         tables [table0, table0 + n_tables) (None = to the last) are replayed on the device from the packed words the arena wrote
         (mj_replay_load_pool), and their Grp is reduced from the same words (mj_pool_grp).  Returns what load_logs returns for the
@@ -395,32 +395,41 @@ class GameplayLoader:
 
         seats: 4-bit seat mask per table (None = all four seats); names: four player names per table (None = ""), filtered by
         player_names / excludes like the names of a log file when given.  oracle=True rebuilds every wall from the table's
-        seed -- logs of this engine always come with their seed, trust_seed does not matter here.  augmented=True is refused:
-        the arena's log is not suit-swapped, and this route has no host encoder that could swap it.
+        seed -- logs of this engine always come with their seed, trust_seed does not matter here.
+
+        augmented=True gives the samples of the suit-swapped game (manzu <-> pinzu, gameplay.rs:126-128): the device swaps the tiles
+        while it copies the log into the replay script, the pool's log stays as it is.  The keyword is per call: the reference builds
+        one loader per pass over its files (mortal/dataloader.py: augmented False, then True), a pool is one object in memory that
+        is read in both forms -- the two passes are two calls on one loader.  Grp holds no tile and is the same in both.  With
+        oracle=True the invisible obs follows the reference's mix, as load_logs does: events swapped, wall as the seed deals it.
+        A loader constructed with augmented=True is refused here (ValueError): pass the keyword instead.
 
         Memory: all obs of the range are materialised on the device at once (137 KB per obs-v4 sample, about 600 samples per
         game and seat), so the caller bounds memory by the table range it asks for."""
         return self._load_device("load_pool", "tables", "pool", pool.n_tables, table0, n_tables, seats, names, type(pool), pool,
                                  pool.log_grp, lambda rp, first, tracked: rp.replay_load_pool(
-                                     pool, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle))
+                                     pool, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle,
+                                     augmented=augmented))
 
-    def load_harvest(self, harvest, game0=0, n_games=None, seats=None, names=None):
+    def load_harvest(self, harvest, game0=0, n_games=None, seats=None, names=None, augmented=False):
         """The samples of the games a pool in refill mode has collected (TablePool.take_harvest), with the contract of load_pool:
         games [game0, game0 + n_games) of the harvest's sorted order (None = to the last) are replayed on the device from the
         collected words (mj_replay_load_harvest), their Grp reduced from the same words (mj_harvest_grp).  Returns a list per game
         of Gameplay, one per wanted seat; the list of a game that ended in error is empty.  seats / names as load_pool.
-        oracle=True deals every wall from the seed recorded with the game.  augmented=True is refused like in load_pool."""
+        oracle=True deals every wall from the seed recorded with the game.  augmented as in load_pool: per call, swapped on the
+        device on the way into the script."""
         harvest._handle()  # (a closed Harvest is refused before anything else)
         return self._load_device("load_harvest", "games", "harvest", harvest.n_games, game0, n_games, seats, names, harvest.pool_cls,
                                  harvest, harvest.grp, lambda rp, first, tracked: rp.replay_load_harvest(
-                                     harvest, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle))
+                                     harvest, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle,
+                                     augmented=augmented))
 
     def _load_device(self, who, unit, where, n_src, first, count, seats, names, pool_cls, src, grp_of, load_into):
         """load_pool / load_harvest: logs [first, first + count) of a device source (`src`: device, deal_algo, log_cap) -> the
         Gameplays.  grp_of(first, n) -> the Grps (None = skipped), load_into(replay pool, first, tracked) loads the scripts."""
         if self.augmented:
-            raise ValueError(f"{who}: augmented=True is not supported (the arena's device log is not suit-swapped and this "
-                             "route has no host encoder to swap it): dump the logs and use load_logs / load_gz_log_files")
+            raise ValueError(f"{who}: a loader constructed with augmented=True is not accepted here (a pool or a harvest is read in "
+                             f"both forms by one loader): construct it without and pass {who}(..., augmented=True) per call")
         n = n_src - first if count is None else int(count)
         if first < 0 or n < 0 or first + n > n_src:
             raise ValueError(f"{who}: {unit} [{first}, {first + n}) are not in a {where} of {n_src}")

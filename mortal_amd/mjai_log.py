@@ -113,6 +113,56 @@ def augment_tile_id(t):
     return {4: 34, 13: 35, 22: 36}[d] if aka else d
 
 
+def _chain_ok(words):
+    """The event chain of packed words is a sequence of known events that ends exactly at the end (mj_gameplay.hip log_walk)."""
+    i, n = 0, len(words)
+    while i < n:
+        w = int(words[i])
+        t = w & 15
+        if not LG_START_KYOKU <= t <= LG_END_KYOKU:
+            return False
+        if t == LG_START_KYOKU:
+            i += 27 if (w >> 63) & 1 else 10
+        else:
+            i += (4 if t == LG_HORA else 3 if t == LG_RYUKYOKU else 1) + ((w >> _TAG_BIT) & 1)
+    return i == n
+
+
+def augment_logs(logs, lib=None):
+    """Event::augment (mjai/event.rs:187-217: manzu <-> pinzu in every tile) of packed logs on the device (mj_augment_logs: the
+    copy kernel of GameplayLoader.load_pool(..., augmented=True)).  logs: a list of uint64 word arrays (TablePool.read_logs,
+    Harvest.read_logs, encode_events; tag words are kept) -> a list of new arrays, an empty log stays empty.  The call is its own
+    inverse.  ValueError names the first malformed log.  `lib` is for the test suite (the host emulation of the same sources)."""
+    import numpy as np
+
+    n = len(logs)
+    if n == 0:
+        return []
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in logs])
+    if int(off[-1]) >= 1 << 32:
+        raise ValueError("augment_logs: more than 2^32 words in one call")
+    off = off.astype(np.uint32)
+    words = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64) for x in logs]), dtype=np.uint64)
+    out = np.empty_like(words)
+    counts = np.zeros(3, dtype=np.int64)
+    stream = None
+    if lib is None:
+        import ctypes
+
+        import torch
+
+        from ._lib import lib
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if lib.mj_augment_logs(words.ctypes.data, off.ctypes.data, n, out.ctypes.data, counts.ctypes.data, stream) < 0:
+        from ._lib import MortalAmdError
+        raise MortalAmdError(lib.mj_last_error().decode())
+    if counts[2]:
+        bad = next((i for i, x in enumerate(logs) if len(x) and not _chain_ok(x)), None)
+        raise ValueError(f"augment_logs: log {bad} is malformed (an unknown event type, or its event chain does not end at its end)")
+    return [out[int(off[i]):int(off[i + 1])].copy() for i in range(n)]
+
+
 def encode_events(events, augmented=False, walls=None, deal_from_seed=False):
     """mjai event dicts (start_game / end_game skipped) -> uint64 words in the LG_* format (inverse of decode_events).
 

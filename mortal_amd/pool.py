@@ -45,6 +45,11 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _load_flags(deal_from_seed, augmented):
+    """include/mortal_amd.h MJ_LOAD_DEAL_FROM_SEED | MJ_LOAD_AUGMENT"""
+    return (1 if deal_from_seed else 0) | (2 if augmented else 0)
+
+
 # include/mortal_amd.h MjHarvestGame
 HARVEST_GAME_DTYPE = np.dtype([("seed_nonce", "<u8"), ("seed_key", "<u8"), ("first_word", "<u8"), ("n_words", "<u4"),
                                ("game_id", "<u4"), ("table", "<u4"), ("cycle", "<u4"), ("scores", "<i4", (4,)), ("err", "u1"),
@@ -256,10 +261,11 @@ class TablePool:
                                  int(always_include_kan_select), n64.ctypes.data if n64 is not None else None,
                                  k64.ctypes.data if k64 is not None else None))
 
-    def replay_load_pool(self, src, table0=0, tracked=None, always_include_kan_select=True, deal_from_seed=False):
+    def replay_load_pool(self, src, table0=0, tracked=None, always_include_kan_select=True, deal_from_seed=False, augmented=False):
         """Load the device logs of src's tables [table0, table0 + self.n_tables) as this pool's replay scripts, on the device
         (mj_replay_load_pool; src needs enable_log).  tracked: 4-bit seat mask per table (None = all four seats);
-        deal_from_seed: the walls are rebuilt from the tables' seeds, which come with the logs (the invisible obs).
+        deal_from_seed: the walls are rebuilt from the tables' seeds, which come with the logs (the invisible obs);
+        augmented: the copy swaps manzu and pinzu in every tile of the script (Event::augment; MJ_LOAD_AUGMENT), src's log stays.
         -> dict(loaded, skipped, malformed): a table still playing or in error is skipped, it replays as an empty log."""
         tr = None
         if tracked is not None:
@@ -270,14 +276,16 @@ class TablePool:
             raise MortalAmdError("replay_load_pool: the source must be a pool of the same library")
         counts = np.zeros(3, dtype=np.int64)
         if self._L.mj_replay_load_pool(self.h, src.h, int(table0), tr.ctypes.data if tr is not None else None,
-                                       int(always_include_kan_select), int(deal_from_seed), counts.ctypes.data, self._stream()) < 0:
+                                       int(always_include_kan_select), _load_flags(deal_from_seed, augmented), counts.ctypes.data,
+                                       self._stream()) < 0:
             raise MortalAmdError(self._L.mj_last_error().decode())
         self.n_rows = [0, 0]
         return dict(loaded=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2]))
 
-    def replay_load_harvest(self, harvest, game0=0, tracked=None, always_include_kan_select=True, deal_from_seed=False):
+    def replay_load_harvest(self, harvest, game0=0, tracked=None, always_include_kan_select=True, deal_from_seed=False,
+                            augmented=False):
         """The same from a Harvest: games [game0, game0 + self.n_tables) of its sorted order (mj_replay_load_harvest); the seeds
-        come from the records.  -> dict(loaded, skipped, malformed): a game in error is skipped."""
+        come from the records; augmented as in replay_load_pool.  -> dict(loaded, skipped, malformed): a game in error is skipped."""
         tr = None
         if tracked is not None:
             tr = np.ascontiguousarray(tracked, dtype=np.uint8)
@@ -287,7 +295,7 @@ class TablePool:
             raise MortalAmdError("replay_load_harvest: the source must be a Harvest of the same library")
         counts = np.zeros(3, dtype=np.int64)
         if self._L.mj_replay_load_harvest(self.h, harvest._handle(), int(game0), tr.ctypes.data if tr is not None else None,
-                                          int(always_include_kan_select), int(deal_from_seed), counts.ctypes.data,
+                                          int(always_include_kan_select), _load_flags(deal_from_seed, augmented), counts.ctypes.data,
                                           self._stream()) < 0:
             raise MortalAmdError(self._L.mj_last_error().decode())
         self.n_rows = [0, 0]

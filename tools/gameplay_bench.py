@@ -12,7 +12,14 @@ One seat per table is tracked by default (--seats 1): every obs of the range is 
 sample, and four seats of 1,024 tables do not fit beside their own reordered copy.
 
 The two routes must give the same samples (checked on the warm-up pair).  No ratio is gated: the file records what came out.
-Writes profiles/pool_gameplay_bench.json.  Needs a GPU; there is no fallback."""
+Writes profiles/pool_gameplay_bench.json.  Needs a GPU; there is no fallback.
+
+--augment-leg instead measures what suit augmentation on the device costs (load_pool(..., augmented=True): the copy kernel swaps the
+tiles on its way): per pool size, on the same finished pool, load_pool plain and augmented, interleaved in this one process, the
+median of the timed pairs after a warm-up pair, with the pack step's own time per call (replay_load_pool: length pass, scan, copy)
+for both.  With --parent-tree DIR (a checkout of the parent commit with its library built) it also alternates child processes of
+this tool on the two trees, each playing the same pool and timing the plain load_pool: the plain path matches the parent when the
+difference of the medians lies inside the spread of the parent's own runs.  Writes profiles/pool_augment_bench.json."""
 import argparse
 import json
 import os
@@ -80,6 +87,114 @@ def commit_of(arg):
         return "unknown"
 
 
+def timed_load(loader, pool, n, mask, names, **kw):
+    """One load_pool call -> (seconds, seconds inside replay_load_pool, samples)."""
+    import numpy as np
+    import torch
+
+    from mortal_amd.pool import TablePool
+
+    pack = Clock()
+    real_pack = TablePool.replay_load_pool
+    TablePool.replay_load_pool = pack.wrap(real_pack)
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = loader.load_pool(pool, seats=np.full(n, mask, dtype=np.uint8), names=[names] * n, **kw)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+    finally:
+        TablePool.replay_load_pool = real_pack
+    n_samples = sum(len(g.actions) for per in got for g in per)
+    del got
+    torch.cuda.empty_cache()
+    return dt, pack.total, n_samples
+
+
+def plain_child(args):
+    """Child of the parent A/B: imports the package of the tree given (this one or the parent's), plays each pool size and times
+    the plain load_pool --repeats times after a warm-up -> one JSON line."""
+    sys.path.insert(0, args.plain_child)
+    from mortal_amd import _lib
+    from mortal_amd.dataset import GameplayLoader
+
+    names = ["a"] * args.seats + ["b"] * (4 - args.seats)
+    loader = GameplayLoader(3, oracle=False, player_names=["a"])
+    out = dict(tree=args.plain_child, library=_lib.LIB_PATH, sizes={})
+    for n in args.tables:
+        pool, _cycles, _play_s = play(n, args.log_words)
+        runs = [timed_load(loader, pool, n, (1 << args.seats) - 1, names) for _ in range(args.repeats)]
+        pool.close()
+        out["sizes"][str(n)] = dict(warm_up_s=runs[0][0], load_pool_s=[r[0] for r in runs[1:]], pack_s=[r[1] for r in runs[1:]],
+                                    samples=runs[0][2])
+    print(json.dumps(out), flush=True)
+
+
+def augment_leg(args):
+    import torch
+
+    from mortal_amd.dataset import GameplayLoader
+
+    names = ["a"] * args.seats + ["b"] * (4 - args.seats)
+    mask = (1 << args.seats) - 1
+    loader = GameplayLoader(3, oracle=False, player_names=["a"])
+    sizes = []
+    for n in args.tables:
+        pool, cycles, play_s = play(n, args.log_words)
+        runs = []
+        for _ in range(args.repeats):
+            p = timed_load(loader, pool, n, mask, names)
+            a = timed_load(loader, pool, n, mask, names, augmented=True)
+            assert p[2] == a[2] > 0  # (the swap changes no sample count)
+            runs.append(dict(plain_load_pool_s=p[0], plain_pack_s=p[1], augmented_load_pool_s=a[0], augmented_pack_s=a[1], samples=p[2]))
+        pool.close()
+        timed = runs[1:]
+        med = {k: statistics.median(x[k] for x in timed) for k in runs[0] if k != "samples"}
+        sizes.append(dict(tables=n, cycles=cycles, play_s=round(play_s, 3), samples=runs[0]["samples"], median=med, warm_up=runs[0],
+                          timed=timed))
+        print(json.dumps(med | dict(tables=n, samples=runs[0]["samples"])), flush=True)
+    ab = None
+    if args.parent_tree:
+        # the plain path against the parent: children alternate between the two trees, new first
+        trees = dict(new=ROOT, parent=os.path.abspath(args.parent_tree))
+        rounds = []
+        for r in range(args.ab_rounds):
+            for which in ("new", "parent"):
+                cmd = [sys.executable, os.path.abspath(__file__), "--plain-child", trees[which], "--repeats", str(args.repeats),
+                       "--seats", str(args.seats), "--log-words", str(args.log_words), "--tables", *map(str, args.tables)]
+                env = {k: v for k, v in os.environ.items() if k != "MORTAL_AMD_LIB"}
+                res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+                if res.returncode != 0:
+                    raise SystemExit(f"plain child on the {which} tree failed ({res.returncode}):\n{res.stderr[-2000:]}")
+                rounds.append(dict(round=r, which=which) | json.loads(res.stdout.strip().splitlines()[-1]))
+        ab = dict(method="child processes alternating new / parent, each plays the pool and times load_pool (plain) "
+                         f"{args.repeats - 1} times after a warm-up; per child the median; spread = max - min of the parent's child medians",
+                  rounds=rounds, sizes={})
+        for n in args.tables:
+            per = {w: [statistics.median(x["sizes"][str(n)]["load_pool_s"]) for x in rounds if x["which"] == w] for w in trees}
+            spread = max(per["parent"]) - min(per["parent"])
+            diff = statistics.median(per["new"]) - statistics.median(per["parent"])
+            ab["sizes"][str(n)] = dict(new_child_medians_s=per["new"], parent_child_medians_s=per["parent"], parent_spread_s=spread,
+                                       new_minus_parent_s=diff, within_parent_spread=abs(diff) <= spread)
+            print(json.dumps(dict(tables=n) | ab["sizes"][str(n)]), flush=True)
+    props = torch.cuda.get_device_properties(0)
+    out = dict(tool="tools/gameplay_bench.py --augment-leg", commit=commit_of(args.commit), obs_version=3, seats_tracked=args.seats,
+               repeats=args.repeats, clock="host perf_counter around each load_pool, device synchronised before and after; pack_s = "
+               "the time inside replay_load_pool (length pass, scan, copy kernel, two synchronises)",
+               box=dict(device=torch.cuda.get_device_name(0), gcn_arch=getattr(props, "gcnArchName", ""), cus=props.multi_processor_count,
+                        torch=torch.__version__, hip=torch.version.hip, cpus_usable=len(os.sched_getaffinity(0))),
+               sizes=sizes, plain_against_parent=ab)
+    path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "pool_augment_bench.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(dict(out=path, commit=out["commit"])))
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "pool_gameplay_bench.json")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--tables", type=int, nargs="+", default=[256, 1024])
@@ -87,10 +202,18 @@ def main():
     ap.add_argument("--seats", type=int, default=1, choices=[1, 2, 3, 4], help="tracked seats per table (seats 0..k-1)")
     ap.add_argument("--log-words", type=int, default=16384)
     ap.add_argument("--commit", default="", help="recorded as given (for a copy of the tree without its history)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pool_gameplay_bench.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--augment-leg", action="store_true", help="load_pool plain against augmented (profiles/pool_augment_bench.json)")
+    ap.add_argument("--parent-tree", default="", help="--augment-leg: a built checkout of the parent commit, for the plain A/B")
+    ap.add_argument("--ab-rounds", type=int, default=3, help="--parent-tree: child processes per tree")
+    ap.add_argument("--plain-child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.repeats < 2:
         raise SystemExit("--repeats: at least 2 (the first pair is the warm-up)")
+    if args.plain_child:
+        return plain_child(args)
+    if args.augment_leg:
+        return augment_leg(args)
 
     import numpy as np
     import torch
