@@ -1,5 +1,6 @@
 // C-ABI host side (include/mortal_amd.h): pool life-cycle and kernel launches.  One translation unit for the whole
-// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip / mj_gameplay.hip / mj_harvest.hip.
+// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip / mj_gameplay.hip / mj_harvest.hip
+// (mj_log.h: what the kernels over packed logs share).
 // Host float math below builds bit-exact LUTs: compile with -ffp-contract=off.
 // Ownership: whatever the host takes from the HIP runtime is held by an owner of mj_host.h and released by its destructor; a call that
 // returns an error leaves the pool as it was before the call (a fallible call builds into locals and moves them in as its last step).
@@ -9,6 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <optional>
 #include <string>
@@ -1121,13 +1123,64 @@ int mj_results(MjPool* P, int32_t* scores, uint8_t* done, void* stream) {
     return 0;
 }
 
-// ---------------------------------------------------------------- Stat over event logs (stat.rs:263-441; mj_stat.hip)
+// ---------------------------------------------------------------- packed event logs as a source (mj_log.h LogSrc)
 namespace {
+// grid of the wavefront-per-log kernels; MJ_LOG_GRID caps it (tests: few workgroups, many logs each)
+int log_grid(size_t n_logs) {
+    int grid = (int)std::min<size_t>((n_logs + LOG_WAVES - 1) / LOG_WAVES, LOG_GRID_MAX);
+    if (const char* v = getenv("MJ_LOG_GRID")) grid = std::min(grid, atoi(v));
+    return std::max(grid, 1);
+}
+// concatenated host logs on the device, with their owners; n_logs == 0: nothing is uploaded and src.n_logs stays 0
+struct HostLogs {
+    DevBuf<uint64_t> words;
+    DevBuf<uint32_t> off;
+    LogSrc src{};
+};
+int upload_logs(const std::string& who, const uint64_t* words_host, const uint32_t* off_host, int n_logs, hipStream_t s, HostLogs& L) {
+    if (n_logs <= 0) return n_logs < 0 ? fail(who + ": negative n_logs") : 0;
+    if (!off_host) return fail(who + ": null offsets");
+    for (int i = 0; i < n_logs; i++)  // the kernels trust the offsets: a log lies inside [0, off[n_logs])
+        if (off_host[i] > off_host[i + 1]) return fail(who + ": offsets of log " + std::to_string(i) + " decrease");
+    const size_t n_words = off_host[n_logs];
+    if (n_words && !words_host) return fail(who + ": null words");
+    if (stat_upload(L.words, words_host, n_words, s) || stat_upload(L.off, off_host, (size_t)n_logs + 1, s)) return -1;
+    L.src.words = L.words.get();
+    L.src.off = L.off.get();
+    L.src.n_logs = n_logs;
+    return 0;
+}
+// tables [table0, table0 + n) of a pool's log as a source, read behind its last step.  `log_of`: how the message names the log;
+// `instead`: what a pool in refill mode is pointed to
+int pool_log_src(const std::string& who, MjPool* P, int table0, int n, hipStream_t s, LogSrc& S,
+                 const char* instead, const char* log_of = "the event log") {
+    if (!P->log) return fail(who + ": " + log_of + " is not enabled (mj_pool_enable_log)");
+    if (P->refill_stride)
+        return fail(who + ": not available in refill mode (a restarted table's log has been rewound; " + instead + " collected games)");
+    if (table0 < 0 || table0 > P->n_tables - n) return fail(who + ": table range out of bounds");
+    if (wait_snapshot(P, s)) return -1;  // behind the last step, whatever its stream
+    S = LogSrc{};
+    S.words = P->log.get();
+    S.len = P->log_len.get();
+    S.stride = P->log_cap;
+    S.blocks = P->blocks.get();
+    S.table0 = table0;
+    S.n_logs = n;
+    return 0;
+}
+
+// ---------------------------------------------------------------- Stat over event logs (stat.rs:263-441; mj_stat.hip)
+int stat_args(int64_t* totals_out, int64_t* counts_out) {
+    if (!totals_out || !counts_out) return fail("null totals / counts buffer");
+    memset(totals_out, 0, 2 * MJ_STAT_FIELDS * sizeof(int64_t));
+    memset(counts_out, 0, 3 * sizeof(int64_t));
+    return 0;
+}
 // launches mj_k_log_stat with K's inputs, copies the outputs to the host and waits for them
 int stat_run(StatParams K, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
              hipStream_t s) {
     if (!totals_out || !counts_out) return fail("null totals / counts buffer");
-    const size_t n = (size_t)K.n_logs, n_out = 2 * MJ_STAT_FIELDS + 3;
+    const size_t n = (size_t)K.src.n_logs, n_out = 2 * MJ_STAT_FIELDS + 3;
     DevBuf<uint8_t> b_seats;
     DevBuf<unsigned long long> b_out;
     DevBuf<long long> b_per;
@@ -1143,8 +1196,7 @@ int stat_run(StatParams K, const uint8_t* seats_host, int64_t* totals_out, int64
         if (b_per.alloc(n * 4 * MJ_STAT_FIELDS)) return -1;
         K.per_seat = b_per.get();
     }
-    const int grid = (int)std::min<size_t>((n + STAT_WAVES - 1) / STAT_WAVES, STAT_GRID_MAX);
-    hipLaunchKernelGGL(mj_k_log_stat, dim3(grid), dim3(STAT_THREADS), 0, s, K);
+    hipLaunchKernelGGL(mj_k_log_stat, dim3(log_grid(n)), dim3(LOG_THREADS), 0, s, K);
     HIP_OK(hipGetLastError());
     int64_t out[2 * MJ_STAT_FIELDS + 3];
     HIP_OK(hipMemcpyAsync(out, b_out.get(), sizeof out, hipMemcpyDeviceToHost, s));
@@ -1159,24 +1211,14 @@ int stat_run(StatParams K, const uint8_t* seats_host, int64_t* totals_out, int64
 
 int mj_stat_logs(const uint64_t* words_host, const uint32_t* off_host, int n_logs, const uint8_t* seats_host,
                  const uint8_t* groups_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3], void* stream) {
-    if (!totals_out || !counts_out) return fail("null totals / counts buffer");
-    memset(totals_out, 0, 2 * MJ_STAT_FIELDS * sizeof(int64_t));
-    memset(counts_out, 0, 3 * sizeof(int64_t));
-    if (n_logs <= 0) return n_logs < 0 ? fail("mj_stat_logs: negative n_logs") : 0;
-    if (!off_host) return fail("mj_stat_logs: null offsets");
-    for (int i = 0; i < n_logs; i++)  // the kernel trusts the offsets: a log lies inside [0, off[n_logs])
-        if (off_host[i] > off_host[i + 1]) return fail("mj_stat_logs: offsets of log " + std::to_string(i) + " decrease");
-    const size_t n_words = off_host[n_logs];
-    if (n_words && !words_host) return fail("mj_stat_logs: null words");
+    if (stat_args(totals_out, counts_out)) return -1;
     hipStream_t s = (hipStream_t)stream;
-    DevBuf<uint64_t> b_words;
-    DevBuf<uint32_t> b_off;
+    HostLogs L;
     DevBuf<uint8_t> b_groups;
-    if (stat_upload(b_words, words_host, n_words, s) || stat_upload(b_off, off_host, (size_t)n_logs + 1, s)) return -1;
+    if (upload_logs("mj_stat_logs", words_host, off_host, n_logs, s, L)) return -1;
+    if (!L.src.n_logs) return 0;
     StatParams K{};
-    K.words = b_words.get();
-    K.off = b_off.get();
-    K.n_logs = n_logs;
+    K.src = L.src;
     if (groups_host) {
         if (stat_upload(b_groups, groups_host, (size_t)n_logs, s)) return -1;
         K.groups = b_groups.get();
@@ -1187,37 +1229,13 @@ int mj_stat_logs(const uint64_t* words_host, const uint32_t* off_host, int n_log
 int mj_pool_stat(MjPool* P, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
                  void* stream) {
     if (!P) return fail("null pool");
-    if (!P->log) return fail("mj_pool_stat: the event log is not enabled (mj_pool_enable_log)");
-    if (P->refill_stride) return fail("mj_pool_stat: not available in refill mode (a restarted table's log has been rewound; mj_harvest_stat reads collected games)");
-    hipStream_t s = (hipStream_t)stream;
-    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));  // behind the last step, whatever its stream
     StatParams K{};
-    K.words = P->log.get();
-    K.len = P->log_len.get();
-    K.stride = P->log_cap;
-    K.blocks = P->blocks.get();
-    K.n_logs = P->n_tables;
-    return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, s);
+    if (pool_log_src("mj_pool_stat", P, 0, P->n_tables, (hipStream_t)stream, K.src, "mj_harvest_stat reads")) return -1;
+    return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- samples and Grp from packed logs (mj_gameplay.hip)
 namespace {
-// grid of the wavefront-per-log kernels; MJ_LOG_GRID caps it (tests: few workgroups, many logs each)
-int log_grid(size_t n_logs) {
-    int grid = (int)std::min<size_t>((n_logs + LOGK_WAVES - 1) / LOGK_WAVES, LOGK_GRID_MAX);
-    if (const char* v = getenv("MJ_LOG_GRID")) grid = std::min(grid, atoi(v));
-    return std::max(grid, 1);
-}
-LogSrc pool_log_src(const MjPool* P, int table0, int n) {
-    LogSrc S{};
-    S.words = P->log.get();
-    S.len = P->log_len.get();
-    S.stride = P->log_cap;
-    S.blocks = P->blocks.get();
-    S.table0 = table0;
-    S.n_logs = n;
-    return S;
-}
 // launches mj_k_log_grp over S, copies the outputs to the host and waits for them
 int grp_run(const LogSrc& S, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out, int32_t* final_out,
             int64_t counts_out[3], hipStream_t s) {
@@ -1228,7 +1246,7 @@ int grp_run(const LogSrc& S, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_
     HIP_OK(hipMemsetAsync(b_feat.get(), 0, n_feat * sizeof(int32_t), s));
     HIP_OK(hipMemsetAsync(b_counts.get(), 0, 3 * sizeof(unsigned long long), s));
     const GrpParams K = {S, max_kyoku, b_feat.get(), b_small.get(), b_small.get() + n, b_small.get() + n * 5, b_counts.get()};
-    hipLaunchKernelGGL(mj_k_log_grp, dim3(log_grid(n)), dim3(LOGK_THREADS), 0, s, K);
+    hipLaunchKernelGGL(mj_k_log_grp, dim3(log_grid(n)), dim3(LOG_THREADS), 0, s, K);
     HIP_OK(hipGetLastError());
     int64_t counts[3];
     HIP_OK(hipMemcpyAsync(feat_out, K.feat, n_feat * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1254,37 +1272,42 @@ int grp_args(const char* who, int n, int max_kyoku, const void* feat, const void
 int mj_grp_logs(const uint64_t* words_host, const uint32_t* off_host, int n_logs, int max_kyoku, int32_t* feat_out,
                 int32_t* n_kyoku_out, int32_t* rank_out, int32_t* final_out, int64_t counts_out[3], void* stream) {
     if (grp_args("mj_grp_logs", n_logs, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out)) return -1;
-    if (n_logs == 0) return 0;
-    if (!off_host) return fail("mj_grp_logs: null offsets");
-    for (int i = 0; i < n_logs; i++)  // the kernel trusts the offsets: a log lies inside [0, off[n_logs])
-        if (off_host[i] > off_host[i + 1]) return fail("mj_grp_logs: offsets of log " + std::to_string(i) + " decrease");
-    const size_t n_words = off_host[n_logs];
-    if (n_words && !words_host) return fail("mj_grp_logs: null words");
     hipStream_t s = (hipStream_t)stream;
-    DevBuf<uint64_t> b_words;
-    DevBuf<uint32_t> b_off;
-    if (stat_upload(b_words, words_host, n_words, s) || stat_upload(b_off, off_host, (size_t)n_logs + 1, s)) return -1;
-    LogSrc S{};
-    S.words = b_words.get();
-    S.off = b_off.get();
-    S.n_logs = n_logs;
-    return grp_run(S, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out, s);
+    HostLogs L;
+    if (upload_logs("mj_grp_logs", words_host, off_host, n_logs, s, L)) return -1;
+    if (!L.src.n_logs) return 0;
+    return grp_run(L.src, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out, s);
 }
 
 int mj_pool_grp(MjPool* P, int table0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
                 int32_t* final_out, int64_t counts_out[3], void* stream) {
     if (!P) return fail("null pool");
     if (grp_args("mj_pool_grp", n, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out)) return -1;
-    if (!P->log) return fail("mj_pool_grp: the event log is not enabled (mj_pool_enable_log)");
-    if (P->refill_stride) return fail("mj_pool_grp: not available in refill mode (a restarted table's log has been rewound; mj_harvest_grp reads collected games)");
-    if (table0 < 0 || table0 > P->n_tables - n) return fail("mj_pool_grp: table range out of bounds");
+    LogSrc S;
+    if (pool_log_src("mj_pool_grp", P, table0, n, (hipStream_t)stream, S, "mj_harvest_grp reads")) return -1;
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));  // behind the last step, whatever its stream
-    return grp_run(pool_log_src(P, table0, n), max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out, s);
+    return grp_run(S, max_kyoku, feat_out, n_kyoku_out, rank_out, final_out, counts_out, (hipStream_t)stream);
 }
 
 namespace {
+// mj_k_log_len -> mj_k_log_scan -> mj_k_log_pack over S: log i goes to out[off[i] .. off[i + 1]), an empty range for a skipped or
+// malformed one.  len [n], off [n + 1]; sums [4], zeroed by the caller: the three counts and the total of words.  `get_out(out)`
+// is asked for the output between scan and pack, so that a caller may size it by the total (it waits for sums[3] itself).
+int log_pack_run(const LogSrc& S, uint32_t* len, uint32_t* off, unsigned long long* sums, const std::function<int(uint64_t*&)>& get_out,
+                 bool augment, int deal_from_seed, hipStream_t s) {
+    const int grid = log_grid((size_t)S.n_logs);
+    const LogLenParams lp = {S, len, sums};
+    hipLaunchKernelGGL(mj_k_log_len, dim3(grid), dim3(LOG_THREADS), 0, s, lp);
+    hipLaunchKernelGGL(mj_k_log_scan, dim3(1), dim3(1024), 0, s, len, S.n_logs, off, sums + 3);
+    HIP_OK(hipGetLastError());
+    uint64_t* out = nullptr;
+    if (get_out(out)) return -1;
+    const LogPackParams pp = {S, off, out, deal_from_seed};
+    if (augment) hipLaunchKernelGGL(mj_k_log_pack<true>, dim3(grid), dim3(LOG_THREADS), 0, s, pp);
+    else hipLaunchKernelGGL(mj_k_log_pack<false>, dim3(grid), dim3(LOG_THREADS), 0, s, pp);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
 // where the destination's tables take their seeds from (deal_from_seed): the source pool's tables, or plain device arrays
 struct SeedSrc {
     const TableBlock* blocks;
@@ -1317,23 +1340,19 @@ int replay_load_src(const std::string& who, MjPool* dst, const LogSrc& S, const 
     HIP_OK(hipMemsetAsync(counters.get(), 0, 8 * sizeof(unsigned long long), s));
     HIP_OK(hipMemsetAsync(sums.get(), 0, 4 * sizeof(unsigned long long), s));
     R.always_kan = always_include_kan_select;
-    const int grid = log_grid((size_t)n);
-    const LogLenParams lp = {S, len.get(), sums.get()};
-    hipLaunchKernelGGL(mj_k_log_len, dim3(grid), dim3(LOGK_THREADS), 0, s, lp);
-    hipLaunchKernelGGL(mj_k_log_scan, dim3(1), dim3(1024), 0, s, len.get(), n, R.off.get(), sums.get() + 3);
     const SeedSrc sd = deal_from_seed ? seeds : SeedSrc{nullptr, 0, nullptr, nullptr};
     hipLaunchKernelGGL(mj_k_log_fresh, dim3(dst->n_blocks), dim3(64), 0, s, blocks.get(), n, sd.blocks, sd.table0, sd.nonces, sd.keys);
-    HIP_OK(hipGetLastError());
     unsigned long long sums_host[4];
-    HIP_OK(hipMemcpyAsync(sums_host, sums.get(), sizeof sums_host, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    if (sums_host[3] > 0xFFFFFFFFull)
-        return fail(who + ": " + std::to_string(sums_host[3]) + " script words do not fit the 32-bit offsets: load fewer tables per call");
-    if (R.script.alloc((size_t)sums_host[3] + 1)) return -1;
-    const LogPackParams pp = {S, R.off.get(), R.script.get(), deal_from_seed};
-    if (flags & MJ_LOAD_AUGMENT) hipLaunchKernelGGL(mj_k_log_pack<true>, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
-    else hipLaunchKernelGGL(mj_k_log_pack<false>, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
-    HIP_OK(hipGetLastError());
+    auto script = [&](uint64_t*& out) {  // allocated once the total is known
+        HIP_OK(hipMemcpyAsync(sums_host, sums.get(), sizeof sums_host, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        if (sums_host[3] > 0xFFFFFFFFull)
+            return fail(who + ": " + std::to_string(sums_host[3]) + " script words do not fit the 32-bit offsets: load fewer tables per call");
+        if (R.script.alloc((size_t)sums_host[3] + 1)) return -1;
+        out = R.script.get();
+        return 0;
+    };
+    if (log_pack_run(S, len.get(), R.off.get(), sums.get(), script, (flags & MJ_LOAD_AUGMENT) != 0, deal_from_seed, s)) return -1;
     HIP_OK(hipStreamSynchronize(s));
     for (int k = 0; k < 3; k++) counts_out[k] = (int64_t)sums_host[k];
     dst->blocks = std::move(blocks);  // (what the destination held goes with the locals)
@@ -1352,15 +1371,12 @@ int mj_replay_load_pool(MjPool* dst, MjPool* src, int table0, const uint8_t* tra
     if (!counts_out) return fail("mj_replay_load_pool: null counts buffer");
     memset(counts_out, 0, 3 * sizeof(int64_t));
     if (src == dst) return fail("mj_replay_load_pool: the source pool cannot be its own destination (the load restarts the destination's tables)");
-    if (!src->log) return fail("mj_replay_load_pool: the event log of the source pool is not enabled (mj_pool_enable_log)");
-    if (src->refill_stride)
-        return fail("mj_replay_load_pool: not available in refill mode (a restarted table's log has been rewound; mj_replay_load_harvest loads collected games)");
-    const int n = dst->n_tables;
-    if (table0 < 0 || table0 > src->n_tables - n) return fail("mj_replay_load_pool: table range out of bounds");
-    hipStream_t s = (hipStream_t)stream;
-    if (src->ev_snap && s != src->step_stream) HIP_OK(hipStreamWaitEvent(s, src->ev_snap.get(), 0));  // behind the source's last step
-    return replay_load_src("mj_replay_load_pool", dst, pool_log_src(src, table0, n), SeedSrc{src->blocks.get(), table0, nullptr, nullptr},
-                           tracked_host, always_include_kan_select, flags, counts_out, s);
+    LogSrc S;
+    if (pool_log_src("mj_replay_load_pool", src, table0, dst->n_tables, (hipStream_t)stream, S, "mj_replay_load_harvest loads",
+                     "the event log of the source pool"))
+        return -1;
+    return replay_load_src("mj_replay_load_pool", dst, S, SeedSrc{src->blocks.get(), table0, nullptr, nullptr}, tracked_host,
+                           always_include_kan_select, flags, counts_out, (hipStream_t)stream);
 }
 
 // Packed host logs through the augmenting copy and back (the pack walk of the loads above, over concatenated logs).  The three
@@ -1369,31 +1385,19 @@ int mj_augment_logs(const uint64_t* words_host, const uint32_t* off_host, int n_
                     void* stream) {
     if (!counts_out) return fail("mj_augment_logs: null counts buffer");
     memset(counts_out, 0, 3 * sizeof(int64_t));
-    if (n_logs <= 0) return n_logs < 0 ? fail("mj_augment_logs: negative n_logs") : 0;
-    if (!off_host) return fail("mj_augment_logs: null offsets");
-    for (int i = 0; i < n_logs; i++)  // the kernel trusts the offsets: a log lies inside [0, off[n_logs])
-        if (off_host[i] > off_host[i + 1]) return fail("mj_augment_logs: offsets of log " + std::to_string(i) + " decrease");
-    const size_t n_words = off_host[n_logs], n = (size_t)n_logs;
-    if (n_words && (!words_host || !words_out_host)) return fail("mj_augment_logs: null words");
     hipStream_t s = (hipStream_t)stream;
-    DevBuf<uint64_t> b_words, b_out;
-    DevBuf<uint32_t> b_off, b_len, b_pack;  // b_pack: the compacted offsets [n + 1]
-    DevBuf<unsigned long long> b_sums;      // done / empty / malformed, total words
-    if (stat_upload(b_words, words_host, n_words, s) || stat_upload(b_off, off_host, n + 1, s) || b_out.alloc(n_words + 1) ||
-        b_len.alloc(n) || b_pack.alloc(n + 1) || b_sums.alloc(4))
-        return -1;
+    HostLogs L;
+    if (upload_logs("mj_augment_logs", words_host, off_host, n_logs, s, L)) return -1;
+    if (!L.src.n_logs) return 0;
+    const size_t n_words = off_host[n_logs], n = (size_t)n_logs;
+    if (n_words && !words_out_host) return fail("mj_augment_logs: null words");
+    DevBuf<uint64_t> b_out;
+    DevBuf<uint32_t> b_len, b_pack;     // b_pack: the compacted offsets [n + 1]
+    DevBuf<unsigned long long> b_sums;  // done / empty / malformed, total words
+    if (b_out.alloc(n_words + 1) || b_len.alloc(n) || b_pack.alloc(n + 1) || b_sums.alloc(4)) return -1;
     HIP_OK(hipMemsetAsync(b_sums.get(), 0, 4 * sizeof(unsigned long long), s));
-    LogSrc S{};
-    S.words = b_words.get();
-    S.off = b_off.get();
-    S.n_logs = n_logs;
-    const int grid = log_grid(n);
-    const LogLenParams lp = {S, b_len.get(), b_sums.get()};
-    hipLaunchKernelGGL(mj_k_log_len, dim3(grid), dim3(LOGK_THREADS), 0, s, lp);
-    hipLaunchKernelGGL(mj_k_log_scan, dim3(1), dim3(1024), 0, s, b_len.get(), n_logs, b_pack.get(), b_sums.get() + 3);
-    const LogPackParams pp = {S, b_pack.get(), b_out.get(), 0};
-    hipLaunchKernelGGL(mj_k_log_pack<true>, dim3(grid), dim3(LOGK_THREADS), 0, s, pp);
-    HIP_OK(hipGetLastError());
+    auto whole = [&](uint64_t*& out) { return out = b_out.get(), 0; };  // (an accepted log's length is its own: never more than n_words)
+    if (log_pack_run(L.src, b_len.get(), b_pack.get(), b_sums.get(), whole, true, 0, s)) return -1;
     std::vector<uint32_t> len(n);
     std::vector<uint64_t> packed(n_words);
     unsigned long long sums_host[4];
@@ -1401,7 +1405,7 @@ int mj_augment_logs(const uint64_t* words_host, const uint32_t* off_host, int n_
     if (n_words) HIP_OK(hipMemcpyAsync(packed.data(), b_out.get(), n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_OK(hipMemcpyAsync(sums_host, b_sums.get(), sizeof sums_host, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    size_t at = 0;  // (an accepted log's length is its own, so the compacted words never outrun n_words)
+    size_t at = 0;
     for (size_t i = 0; i < n; i++) {
         const size_t lo = off_host[i], k = off_host[i + 1] - lo;
         if (len[i] == k && k) memcpy(words_out_host + lo, packed.data() + at, k * sizeof(uint64_t)), at += k;
@@ -1436,7 +1440,7 @@ int mj_harvest_pending(MjPool* P, int64_t out[3], void* stream) {
     if (!P || !out) return fail("null pool / output");
     if (!P->hv.games) return fail("mj_harvest_pending: harvesting is not enabled (mj_pool_enable_harvest)");
     hipStream_t s = (hipStream_t)stream;
-    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));
+    if (wait_snapshot(P, s)) return -1;
     unsigned long long c[HV_CURSORS];
     HIP_OK(hipMemcpyAsync(c, P->hv.cursors.get(), sizeof c, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
@@ -1449,7 +1453,7 @@ int mj_harvest_take(MjPool* P, MjHarvest** out, void* stream) {
     *out = nullptr;
     if (!P->hv.games) return fail("mj_harvest_take: harvesting is not enabled (mj_pool_enable_harvest)");
     hipStream_t s = (hipStream_t)stream;
-    if (P->ev_snap && s != P->step_stream) HIP_OK(hipStreamWaitEvent(s, P->ev_snap.get(), 0));  // behind the last step, whatever its stream
+    if (wait_snapshot(P, s)) return -1;  // behind the last step, whatever its stream
     // the replacement first; the pool keeps its buffer until nothing can fail any more
     HarvestBuf fresh;
     if (fresh.alloc(P->hv.max_games, P->hv.max_words, s)) return -1;
@@ -1509,22 +1513,6 @@ int mj_harvest_read(const MjHarvest* h, int game, uint64_t* words_out) {
     return 0;
 }
 
-int mj_harvest_stat(const MjHarvest* h, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
-                    void* stream) {
-    if (!h) return fail("null harvest");
-    if (!totals_out || !counts_out) return fail("null totals / counts buffer");
-    memset(totals_out, 0, 2 * MJ_STAT_FIELDS * sizeof(int64_t));
-    memset(counts_out, 0, 3 * sizeof(int64_t));
-    if (h->games.empty()) return 0;
-    StatParams K{};
-    K.words = h->buf.words.get();
-    K.start = h->start.get();
-    K.len = h->len.get();
-    K.groups = h->group.get();
-    K.n_logs = (int)h->games.size();
-    return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, (hipStream_t)stream);
-}
-
 namespace {
 LogSrc harvest_log_src(const MjHarvest* h, int game0, int n) {
     LogSrc S{};
@@ -1535,6 +1523,17 @@ LogSrc harvest_log_src(const MjHarvest* h, int game0, int n) {
     return S;
 }
 }  // namespace
+
+int mj_harvest_stat(const MjHarvest* h, const uint8_t* seats_host, int64_t* totals_out, int64_t* per_seat_out, int64_t counts_out[3],
+                    void* stream) {
+    if (!h) return fail("null harvest");
+    if (stat_args(totals_out, counts_out)) return -1;
+    if (h->games.empty()) return 0;
+    StatParams K{};
+    K.src = harvest_log_src(h, 0, (int)h->games.size());
+    K.groups = h->group.get();
+    return stat_run(K, seats_host, totals_out, per_seat_out, counts_out, (hipStream_t)stream);
+}
 
 int mj_harvest_grp(const MjHarvest* h, int game0, int n, int max_kyoku, int32_t* feat_out, int32_t* n_kyoku_out, int32_t* rank_out,
                    int32_t* final_out, int64_t counts_out[3], void* stream) {

@@ -3,66 +3,15 @@
 // mj_k_log_scan, mj_k_log_pack, mj_k_log_fresh), and dataset/grp.rs:90-164 Grp::load_events is reduced from the same words
 // (mj_k_log_grp).
 //
-// Shape, as mj_k_log_stat (mj_stat.hip): one wavefront handles one log at a time, grid-stride over the logs; the 64 lanes load 64
-// consecutive words as one coalesced 512-byte read and the chain of events is followed with wave-uniform __shfl reads of those
-// registers -- no lane streams a log of its own.  An event's length is a function of its header word alone (mj_replay.hip rp_len),
-// so the length pass and the copy walk fixed windows [64 j, 64 j + 64) and carry the chain position across them; the copy stores
-// each window as it was loaded (coalesced), with LG_SK_DEAL_BIT set on the lanes the walk found to hold a start_kyoku header (a
-// payload word can look like one: the headers are known only by walking).  Grp reads payload words (scores, deltas), so
-// mj_k_log_grp restarts its window at an event whose first two payload words could lie outside it, like mj_k_log_stat.
+// Shape: mj_log.h.  An event's length is a function of its header word alone (log_event_len), so the length pass and the copy walk
+// fixed windows [64 j, 64 j + 64) and carry the chain position across them; the copy stores each window as it was loaded
+// (coalesced), with LG_SK_DEAL_BIT set on the lanes the walk found to hold a start_kyoku header (a payload word can look like one:
+// the headers are known only by walking).  Grp reads payload words (scores, deltas): mj_k_log_grp is a callable of log_walk_events.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mj_algo.h"
-#include "mj_stat.hip"
-
-#define LOGK_WAVES 4                 // wavefronts (= logs in flight) per workgroup
-#define LOGK_THREADS (64 * LOGK_WAVES)
-#define LOGK_GRID_MAX (256 * 4)      // bounded grid, the rest by grid stride (MJ_LOG_GRID lowers it: tests)
-#define LOGK_WINDOW_LAST 60          // mj_k_log_grp: header + tag + two payload words <= window index 63
-
-// The three addressings of StatParams: concatenated logs with `off`, tables [table0, table0 + n_logs) of a pool's strided log, or
-// scattered logs of a harvest (mj_harvest.hip) with `start`.
-struct LogSrc {
-    const uint64_t* words;
-    const uint32_t* off;         // [n_logs + 1], or NULL: log i is table table0 + i, at words + table * stride ...
-    const uint32_t* len;         // ... with len[table] words; more than stride = the log overflowed: malformed
-    uint32_t stride;
-    const TableBlock* blocks;    // pool path: flags / err of the table
-    int table0;
-    int n_logs;
-    const uint64_t* start;       // [n_logs], or NULL; scattered: log i is words + start[i] with len[i] words, len[i] == 0 = skipped
-};
-enum { LOG_OK = 0, LOG_SKIP = 1, LOG_BAD = 2 };
-
-// log i -> its words and length; LOG_SKIP: nothing to read (an empty log; a table whose game has not finished without an error,
-// tested as mj_k_log_stat tests it), LOG_BAD: log_len beyond log_cap
-MJD int log_locate(const LogSrc& S, int i, const uint64_t*& lw, uint32_t& len) {
-    if (S.off) {
-        lw = S.words + (size_t)S.off[i];
-        len = S.off[i + 1] - S.off[i];
-        return len ? LOG_OK : LOG_SKIP;
-    }
-    if (S.start) {
-        lw = S.words + (size_t)S.start[i];
-        len = S.len[i];
-        return len ? LOG_OK : LOG_SKIP;
-    }
-    const int t = S.table0 + i;
-    lw = S.words + (size_t)t * S.stride;
-    len = S.len[t];
-    const TableBlock* B = S.blocks + (t >> 6);
-    const uint32_t fl = B->flags[t & 63];
-    if (!(fl & TF_DONE) || (fl & TF_INACTIVE) || B->err[t & 63] != MJ_OK || len == 0) return LOG_SKIP;
-    return len > S.stride ? LOG_BAD : LOG_OK;
-}
-
-MJD int log_event_len(uint32_t w_lo, uint32_t w_hi) {  // mj_replay.hip rp_len
-    const int t = w_lo & 15;
-    if (t == LG_START_KYOKU) return (w_hi >> (LG_SK_WALL_BIT - 32)) & 1 ? 27 : 10;
-    return (t == LG_HORA ? 4 : t == LG_RYUKYOKU ? 3 : 1) + (int)((w_hi >> (LG_TAG_BIT - 32)) & 1);
-}
+#include "mj_log.h"
 
 // ---- suit augmentation on the way through (the reference's GameplayLoader(augmented=True): mjai/event.rs:187-217 Event::augment,
 // tile.rs:154-167 Tile::augment).  What a word is -- a header, haipai tiles, wall tiles, ura indicators, or a tag / score / delta
@@ -125,7 +74,7 @@ MJD uint64_t log_aug_word(uint64_t w, const LogRoles& R, int lane, bool deal) {
     return w;
 }
 
-// Walks the chain of one log in fixed 64-word windows.  `store`: NULL, or where the words go; `deal_bit`: set LG_SK_DEAL_BIT in
+// Walks the chain of one log in fixed 64-word windows (it reads no payload, so unlike log_walk_events it never restarts one).  `store`: NULL, or where the words go; `deal_bit`: set LG_SK_DEAL_BIT in
 // every start_kyoku header on the way.  -> the chain is a sequence of known events that ends exactly at `len`.
 // AUG: the stored words are suit-augmented (above), and `deal_bit` sets LG_SK_AUG_BIT as well; the plain walk is what it was.
 template <bool AUG>
@@ -142,12 +91,9 @@ MJD bool log_walk(const uint64_t* lw, uint32_t len, int lane, uint64_t* store, b
             if (pos > base) log_roles_add(R, ev_pos, ev_lo, ev_hi, base);  // the payload the previous window left behind
         while (pos < end && !bad) {
             const int k = __builtin_amdgcn_readfirstlane((int)(pos - base));
-            const uint64_t wv = __shfl(mine, k);
-            const uint32_t w_lo = __builtin_amdgcn_readfirstlane((uint32_t)wv);
-            const uint32_t w_hi = __builtin_amdgcn_readfirstlane((uint32_t)(wv >> 32));
-            const int t = w_lo & 15;
-            if (t < LG_START_KYOKU || t > LG_END_KYOKU) bad = true;
-            if (t == LG_START_KYOKU) sk |= 1ull << k;
+            uint32_t w_lo, w_hi;
+            if (!log_header(mine, k, w_lo, w_hi)) bad = true;
+            if ((w_lo & 15) == LG_START_KYOKU) sk |= 1ull << k;
             if constexpr (AUG) {
                 R.hdr |= 1ull << k;
                 log_roles_add(R, pos, w_lo, w_hi, base);
@@ -172,19 +118,18 @@ struct LogLenParams {
     uint32_t* len_out;           // [n_logs]
     unsigned long long* counts;  // [3] loaded / skipped / malformed, added to
 };
-__global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_len(LogLenParams P) {
+__global__ __launch_bounds__(LOG_THREADS) void mj_k_log_len(LogLenParams P) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned n_ok = 0, n_skip = 0, n_bad = 0;
-    for (int i = blockIdx.x * LOGK_WAVES + wave; i < P.src.n_logs; i += gridDim.x * LOGK_WAVES) {
+    LogCounts n;
+    for (int i = blockIdx.x * LOG_WAVES + wave; i < P.src.n_logs; i += gridDim.x * LOG_WAVES) {
         const uint64_t* lw;
         uint32_t len;
         int st = log_locate(P.src, i, lw, len);
         if (st == LOG_OK && !log_walk<false>(lw, len, lane, nullptr, false)) st = LOG_BAD;
         if (lane == 0) P.len_out[i] = st == LOG_OK ? len : 0u;
-        n_ok += st == LOG_OK, n_skip += st == LOG_SKIP, n_bad += st == LOG_BAD;
+        n.add(st);
     }
-    const unsigned n_mine = lane == 0 ? n_ok : lane == 1 ? n_skip : n_bad;  // one count per lane
-    if (lane < 3 && n_mine) atomicAdd(&P.counts[lane], (unsigned long long)n_mine);
+    n.flush(lane, P.counts);
 }
 
 // ---- pass 2: exclusive scan of the lengths, one workgroup; off[n] = the total's low word, *total = the total
@@ -227,9 +172,9 @@ struct LogPackParams {
 // AUG: the words go through the suit swap (log_walk<true>); the plain instantiation is the copy it was
 
 template <bool AUG>
-__global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_pack(LogPackParams P) {
+__global__ __launch_bounds__(LOG_THREADS) void mj_k_log_pack(LogPackParams P) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = blockIdx.x * LOGK_WAVES + wave; i < P.src.n_logs; i += gridDim.x * LOGK_WAVES) {
+    for (int i = blockIdx.x * LOG_WAVES + wave; i < P.src.n_logs; i += gridDim.x * LOG_WAVES) {
         const uint32_t n = P.off[i + 1] - P.off[i];
         if (n == 0) continue;
         const uint64_t* lw;
@@ -278,57 +223,29 @@ struct GrpParams {
     int32_t* final_;    // [n_logs][4] final_scores
     unsigned long long* counts;  // [3] reduced / skipped / malformed, added to
 };
-__global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_grp(GrpParams P) {
+__global__ __launch_bounds__(LOG_THREADS) void mj_k_log_grp(GrpParams P) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pid = lane & 3;
-    unsigned n_ok = 0, n_skip = 0, n_bad = 0;
-    for (int log = blockIdx.x * LOGK_WAVES + wave; log < P.src.n_logs; log += gridDim.x * LOGK_WAVES) {
+    LogCounts n;
+    for (int log = blockIdx.x * LOG_WAVES + wave; log < P.src.n_logs; log += gridDim.x * LOG_WAVES) {
         const uint64_t* lw;
         uint32_t len;
         int st = log_locate(P.src, log, lw, len);
         int32_t* const F = P.feat + (size_t)log * P.max_kyoku * 7;
-        int nk = 0, cur0 = 0, cur1 = 0, cur2 = 0, cur3 = 0;  // wave-uniform
+        int nk = 0;  // wave-uniform
+        LogScores sc;
         if (st == LOG_OK) {
-            bool bad = false;
-            uint32_t pos = 0;
-            while (pos < len && !bad) {
-                const uint32_t base = pos;
-                const uint64_t mine = base + (uint32_t)lane < len ? lw[base + lane] : 0ull;  // never beyond len
-                while (pos < len && pos - base <= LOGK_WINDOW_LAST) {
-                    const int k = __builtin_amdgcn_readfirstlane((int)(pos - base));
-                    const uint64_t wv = __shfl(mine, k);
-                    const uint32_t w_lo = __builtin_amdgcn_readfirstlane((uint32_t)wv);
-                    const uint32_t w_hi = __builtin_amdgcn_readfirstlane((uint32_t)(wv >> 32));
-                    const int t = w_lo & 15, actor = (w_lo >> 4) & 3;
-                    if (t < LG_START_KYOKU || t > LG_END_KYOKU) { bad = true; break; }
-                    const uint32_t next = pos + (uint32_t)log_event_len(w_lo, w_hi);
-                    if (next > len) { bad = true; break; }  // the chain runs past the end of the log
-                    pos = next;
-                    if (t != LG_START_KYOKU && t != LG_HORA && t != LG_RYUKYOKU) {
-                        if (t == LG_REACH_ACCEPTED) {
-                            cur0 -= actor == 0 ? 1000 : 0, cur1 -= actor == 1 ? 1000 : 0;
-                            cur2 -= actor == 2 ? 1000 : 0, cur3 -= actor == 3 ? 1000 : 0;
-                        }
-                        continue;
-                    }
-                    const int p = k + 1 + (t != LG_START_KYOKU ? (int)((w_hi >> (LG_TAG_BIT - 32)) & 1) : 0);  // first payload word
-                    const uint64_t a = __shfl(mine, p), b = __shfl(mine, p + 1);
-                    const int d0 = (int)(uint32_t)a, d1 = (int)(uint32_t)(a >> 32), d2 = (int)(uint32_t)b, d3 = (int)(uint32_t)(b >> 32);
-                    if (t != LG_START_KYOKU) {
-                        cur0 += d0, cur1 += d1, cur2 += d2, cur3 += d3;
-                        continue;
-                    }
-                    if (nk >= P.max_kyoku) { bad = true; break; }
-                    const int c0 = (w_lo >> 14) & 63;  // bakaze * 4 + kyoku - 1; grp.rs:135-139 counts west and north alike
-                    const int grand = c0 < 12 ? c0 : c0 - 4;
-                    const int honba = (w_hi >> (LG_HONBA_SHIFT - 32)) & 0xFF, kyotaku = (w_hi >> (LG_KYOTAKU_SHIFT - 32)) & 0xFF;
-                    if (lane < 7)
-                        F[nk * 7 + lane] = lane == 0 ? grand : lane == 1 ? honba : lane == 2 ? kyotaku : stat_pick(lane - 3, d0, d1, d2, d3);
-                    nk++;
-                    cur0 = d0, cur1 = d1, cur2 = d2, cur3 = d3;
-                }
-            }
-            if (bad || nk == 0) {
+            const bool ok = log_walk_events(lw, len, lane, sc, [&](const LogEvent& e) {
+                if (e.type != LG_START_KYOKU) return true;
+                if (nk >= P.max_kyoku) return false;
+                const int c0 = (e.w_lo >> 14) & 63;  // bakaze * 4 + kyoku - 1; grp.rs:135-139 counts west and north alike
+                const int grand = c0 < 12 ? c0 : c0 - 4;
+                const int honba = (e.w_hi >> (LG_HONBA_SHIFT - 32)) & 0xFF, kyotaku = (e.w_hi >> (LG_KYOTAKU_SHIFT - 32)) & 0xFF;
+                if (lane < 7)
+                    F[nk * 7 + lane] = lane == 0 ? grand : lane == 1 ? honba : lane == 2 ? kyotaku : log_pick(lane - 3, e.d0, e.d1, e.d2, e.d3);
+                nk++;
+                return true;
+            });
+            if (!ok || nk == 0) {
                 st = LOG_BAD;
                 for (int r = 0; r < nk; r++)  // (the lanes that wrote the rows take them back)
                     if (lane < 7) F[r * 7 + lane] = 0;
@@ -336,20 +253,12 @@ __global__ __launch_bounds__(LOGK_THREADS) void mj_k_log_grp(GrpParams P) {
         }
         if (lane < 4) {
             int rank = 0, final_score = 0;
-            if (st == LOG_OK) {
-                // Rankings::new: stable, ties to the lower seat; the top-up to 100,000 goes to first place after ranking
-                const int mine_c = stat_pick(pid, cur0, cur1, cur2, cur3);
-                rank = (cur0 > mine_c || (cur0 == mine_c && 0 < pid)) + (cur1 > mine_c || (cur1 == mine_c && 1 < pid)) +
-                       (cur2 > mine_c || (cur2 == mine_c && 2 < pid)) + (cur3 > mine_c || (cur3 == mine_c && 3 < pid));
-                const int total = cur0 + cur1 + cur2 + cur3;
-                final_score = mine_c + (rank == 0 && total < 100000 ? 100000 - total : 0);
-            }
+            if (st == LOG_OK) sc.final_of(lane, rank, final_score);
             P.rank[(size_t)log * 4 + lane] = rank;
             P.final_[(size_t)log * 4 + lane] = final_score;
         }
         if (lane == 0) P.n_kyoku[log] = st == LOG_OK ? nk : st == LOG_SKIP ? 0 : -1;
-        n_ok += st == LOG_OK, n_skip += st == LOG_SKIP, n_bad += st == LOG_BAD;
+        n.add(st);
     }
-    const unsigned n_mine = lane == 0 ? n_ok : lane == 1 ? n_skip : n_bad;  // one count per lane
-    if (lane < 3 && n_mine) atomicAdd(&P.counts[lane], (unsigned long long)n_mine);
+    n.flush(lane, P.counts);
 }

@@ -2,7 +2,7 @@
 // arena/game.rs:291-296, and keeps seed, scores and log with it, arena/result.rs:19-51).  mj_k_refill rewinds a finished table's log
 // in the step after the one that finished it; mj_k_harvest runs directly in front of it and copies what is about to be rewound --
 // the log's words, the seed, the final scores -- into the pool's harvest buffer.  The reducers (mj_k_log_stat, mj_k_log_grp) and
-// the replay loader then read the buffer through the scattered addressing of StatParams / LogSrc.
+// the replay loader then read the buffer through the scattered addressing of LogSrc (mj_log.h).
 //
 // Shape, as mj_k_refill: one 64-lane workgroup per TableBlock.  The wavefront ballots the lanes whose table is about to be restarted
 // and loops over the set bits wave-uniformly; for each game its own lane reserves a word range and a record slot on the buffer's two

@@ -7,6 +7,7 @@
 // (gameplay.rs:296-409: the next event, with the reach_accepted / dora skip and the hora look-ahead).
 #include <hip/hip_runtime.h>
 
+#include "mj_log.h"
 #include "mj_rules.h"
 
 struct ReplayParams {
@@ -29,11 +30,6 @@ struct ReplayParams {
 struct RpEvent {
     int type, actor, target, pai, c[4], tsumogiri, len;
 };
-MJD int rp_len(uint64_t w) {
-    const int t = (int)(w & 15);
-    const int tag = (int)((w >> LG_TAG_BIT) & 1);  // arena logs fed back as scripts: the tag word is skipped
-    return t == LG_START_KYOKU ? (((w >> LG_SK_WALL_BIT) & 1) ? 27 : 10) : (t == LG_HORA ? 4 : t == LG_RYUKYOKU ? 3 : 1) + tag;
-}
 MJD RpEvent rp_decode(uint64_t w) {
     RpEvent e;
     e.type = (int)(w & 15);
@@ -42,7 +38,7 @@ MJD RpEvent rp_decode(uint64_t w) {
     e.pai = (int)((w >> 8) & 63);
     for (int k = 0; k < 4; k++) e.c[k] = (int)((w >> (14 + 6 * k)) & 63);
     e.tsumogiri = (int)((w >> 38) & 1);
-    e.len = rp_len(w);
+    e.len = log_event_len((uint32_t)w, (uint32_t)(w >> 32));  // (arena logs fed back as scripts: the tag word is skipped)
     return e;
 }
 

@@ -152,6 +152,106 @@ def check_alignment_sweep(lib):
         check(logs, lib, want=want)
 
 
+def check_alignment_sweep_grp(lib):
+    """The same 2 x 128 synthetic logs through grp_logs against the host `Grp.load_events`: the shared walk's window restart
+    (an event at window index 60 / 61 among them) under its second consumer."""
+    from mortal_amd.dataset import Grp, grp_logs
+
+    for tagged in (False, True):
+        pairs = [(k, lead) for k in range(64) for lead in (0, 1)]
+        logs = [synthetic_words(k, lead, tagged) for k, lead in pairs]
+        grps, n_kyoku, counts = grp_logs(logs, max_kyoku=2, lib=lib)
+        assert counts == dict(reduced=len(logs), skipped=0, malformed=0), counts
+        assert (n_kyoku == 2).all()
+        for g, (k, lead) in zip(grps, pairs):
+            want = Grp.load_events(ML.decode_events(synthetic_words(k, lead, tagged)))
+            assert want.feature.shape == (2, 7) and sum(want.final_scores) == 100_000
+            assert (g.feature.view(np.uint64) == want.feature.view(np.uint64)).all(), (tagged, k, lead)
+            assert g.rank_by_player == want.rank_by_player and g.final_scores == want.final_scores, (tagged, k, lead)
+
+
+# ---- (d) bad and empty input: ten logs, read by all three routes
+def check_bad_and_empty_input(lib):
+    """A log cut inside a hora payload, one cut inside a start_kyoku payload and headers of type 15 / 0 are counted as malformed
+    and contribute nothing; an empty log is skipped; their neighbours are reduced as if they stood alone.  No route reads beyond a
+    log's length, so this is a contained error path.  Stat (stat_logs), Grp (grp_logs / Grp.from_packed) and the augmenting copy
+    (mjai_log.augment_logs / mj_augment_logs) agree on the ten: logs 0, 2, 4, 6, 9 accepted, log 5 skipped, logs 1, 3, 7, 8
+    malformed -- counts 5 / 1 / 4.  Grp's two extra rules: every accepted log has two start_kyoku, so none falls under "no
+    start_kyoku", and with max_kyoku = 1 the five become malformed as well (0 / 1 / 9)."""
+    import pytest
+
+    from mortal_amd.dataset import Grp, grp_logs
+
+    good = [synthetic_words(k, 0, tagged) for k, tagged in ((0, False), (31, True), (5, False), (62, True), (17, False))]
+    base = synthetic_words(29, 1, False)
+    hora = next(i for i, w in enumerate(base) if int(w) & 15 == ML.LG_HORA and i > 60)
+    assert ML.decode_events(base[:hora])[-1]["type"] == "dahai"  # (a header found by walking, not a payload word that looks like one)
+    cut_hora = base[:hora + 2]
+    cut_start = base[:6]
+    type15 = np.concatenate([base[:hora], np.array([15], dtype=np.uint64), base[hora:]])
+    type0 = np.concatenate([base, np.array([0], dtype=np.uint64)])
+    empty = np.zeros(0, dtype=np.uint64)
+    logs = [good[0], cut_hora, good[1], type15, good[2], empty, good[3], type0, cut_start, good[4]]
+    for w in (cut_hora, cut_start, type15, type0):
+        with pytest.raises((IndexError, ValueError)):
+            ML.decode_events(w)
+    is_good, is_bad = [0, 2, 4, 6, 9], [1, 3, 7, 8]
+    # Stat
+    want = np.zeros((len(logs), 4, NF), dtype=np.int64)
+    want[is_good] = expected(good)
+    groups = np.array([1, 15, 2, 15, 4, 15, 8, 15, 15, 0], dtype=np.uint8)
+    totals, rows, counts = stat_logs(logs, groups=groups, per_seat=True, lib=lib)
+    assert counts == dict(reduced=5, skipped=1, malformed=4), counts
+    assert (rows == want).all()
+    assert (np.array([t.counters() for t in totals]) == totals_of(want, np.full(len(logs), 15), groups)).all()
+    assert totals[0].game == 16 and totals[1].game == 4
+    # Grp
+    grps, n_kyoku, counts = grp_logs(logs, lib=lib)
+    assert counts == dict(reduced=5, skipped=1, malformed=4), counts
+    assert n_kyoku.tolist() == [2, -1, 2, -1, 2, 0, 2, -1, -1, 2]
+    for i, g in enumerate(grps):
+        if i in is_good:
+            w = Grp.load_events(ML.decode_events(logs[i]))
+            assert (g.feature.view(np.uint64) == w.feature.view(np.uint64)).all() and g.rank_by_player == w.rank_by_player \
+                and g.final_scores == w.final_scores, i
+        else:
+            assert g is None, i
+    with pytest.raises(ValueError, match="log 1"):
+        Grp.from_packed(logs, lib=lib)
+    grps, n_kyoku, counts = grp_logs(logs, max_kyoku=1, lib=lib)
+    assert counts == dict(reduced=0, skipped=1, malformed=9) and grps == [None] * 10
+    assert n_kyoku.tolist() == [-1, -1, -1, -1, -1, 0, -1, -1, -1, -1]
+    # the augmenting copy: an accepted log comes back augmented (as it does alone), the others as they came
+    with pytest.raises(ValueError, match="log 1 is malformed"):
+        ML.augment_logs(logs, lib=lib)
+    alone = ML.augment_logs(good, lib=lib)
+    off = np.zeros(len(logs) + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(x) for x in logs])
+    words = np.ascontiguousarray(np.concatenate(logs), dtype=np.uint64)
+    out = np.full_like(words, 0x5A5A)
+    counts = np.full(3, 7, dtype=np.int64)
+    stream = None
+    if lib is None:
+        import ctypes
+
+        import torch
+
+        from mortal_amd._lib import lib
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.mj_augment_logs(words.ctypes.data, off.ctypes.data, len(logs), out.ctypes.data, counts.ctypes.data, stream) == 0
+    assert counts.tolist() == [5, 1, 4]
+    for i in range(len(logs)):
+        got = out[int(off[i]):int(off[i + 1])]
+        if i in is_good:
+            assert (got == alone[is_good.index(i)]).all() and (got != logs[i]).any(), i
+        else:
+            assert (got == logs[i]).all(), i
+    assert sorted(is_good + is_bad + [5]) == list(range(10))
+    # nothing at all
+    totals, rows, counts = stat_logs([], per_seat=True, lib=lib)
+    assert totals[0] == totals[1] == Stat() and rows.shape == (0, 4, 44) and counts == dict(reduced=0, skipped=0, malformed=0)
+
+
 # ---- the pool path: TablePool.log_stat on the log the step kernel wrote (tag words on every decision)
 def check_pool(pool_cls, n, probe_cycle=40, max_cycles=8000):
     """n tables, obs v3, both agents on the device's greedy policy, log on, to completion: log_stat against the host reading of

@@ -22,6 +22,14 @@ def test_alignment_sweep():
     S.check_alignment_sweep(None)
 
 
+def test_alignment_sweep_grp():
+    S.check_alignment_sweep_grp(None)
+
+
+def test_bad_and_empty_input():
+    S.check_bad_and_empty_input(None)
+
+
 def test_more_logs_than_one_grid_pass(oracle):
     """5,003 logs (the 44 fixture logs repeated): not a multiple of the four wavefronts of a workgroup and more than the bounded
     grid takes in one pass, so wavefronts chain logs and the last workgroup is partly idle."""

@@ -52,37 +52,12 @@ def test_alignment_sweep(emu):
     S.check_alignment_sweep(emu._L)
 
 
-def test_bad_and_empty_input(emu):
-    """A log cut inside a hora payload, one cut inside a start_kyoku payload and headers of type 15 / 0 are counted as malformed
-    and contribute nothing; an empty log is skipped; their neighbours are reduced as if they stood alone."""
-    from mortal_amd import mjai_log as ML
-    from mortal_amd.stat import Stat, stat_logs
+def test_alignment_sweep_grp(emu):
+    S.check_alignment_sweep_grp(emu._L)
 
-    good = [S.synthetic_words(k, 0, tagged) for k, tagged in ((0, False), (31, True), (5, False), (62, True), (17, False))]
-    base = S.synthetic_words(29, 1, False)
-    hora = next(i for i, w in enumerate(base) if int(w) & 15 == ML.LG_HORA and i > 60)
-    assert ML.decode_events(base[:hora])[-1]["type"] == "dahai"  # (a header found by walking, not a payload word that looks like one)
-    cut_hora = base[:hora + 2]
-    cut_start = base[:6]
-    type15 = np.concatenate([base[:hora], np.array([15], dtype=np.uint64), base[hora:]])
-    type0 = np.concatenate([base, np.array([0], dtype=np.uint64)])
-    empty = np.zeros(0, dtype=np.uint64)
-    logs = [good[0], cut_hora, good[1], type15, good[2], empty, good[3], type0, cut_start, good[4]]
-    for w in (cut_hora, cut_start, type15, type0):
-        with pytest.raises((IndexError, ValueError)):
-            ML.decode_events(w)
-    is_good = [0, 2, 4, 6, 9]
-    want = np.zeros((len(logs), 4, S.NF), dtype=np.int64)
-    want[is_good] = S.expected(good)
-    groups = np.array([1, 15, 2, 15, 4, 15, 8, 15, 15, 0], dtype=np.uint8)
-    totals, rows, counts = stat_logs(logs, groups=groups, per_seat=True, lib=emu._L)
-    assert counts == dict(reduced=5, skipped=1, malformed=4), counts
-    assert (rows == want).all()
-    assert (np.array([t.counters() for t in totals]) == S.totals_of(want, np.full(len(logs), 15), groups)).all()
-    assert totals[0].game == 16 and totals[1].game == 4
-    # nothing at all
-    totals, rows, counts = stat_logs([], per_seat=True, lib=emu._L)
-    assert totals[0] == totals[1] == Stat() and rows.shape == (0, 4, 44) and counts == dict(reduced=0, skipped=0, malformed=0)
+
+def test_bad_and_empty_input(emu):
+    S.check_bad_and_empty_input(emu._L)
 
 
 def test_pool_log_stat(emu):
