@@ -3,18 +3,19 @@ and `mortal_amd.mjai_log.decode_events` produce, a whole hanchan or a prefix of 
 
 Pure Python on the events alone: neither the oracle nor the device code is asked anything, so the census can judge both.  The
 names are those of SITUATIONS below; a key that starts with "mismatch:" means the log contradicts the rule the census derived from
-the events themselves (exhaustive-draw payments from the seats' hands and discards, the payer of a pao win), and no log of a correct
-engine holds one.
+the events themselves (exhaustive-draw payments from the seats' hands and discards, the payer of a pao win, the abort after four
+equal winds), and no log of a correct engine holds one.
 
-Rule references: the reference's arena/board.rs (step :511-678, exhaustive_ryukyoku :241-294, handle_hora :366-471, update_paos :473-499)."""
+Rule references: the reference's arena/board.rs (step :511-678, exhaustive_ryukyoku :241-294, update_nagashi_mangan_and_four_wind
+and check_four_wind :296-340, handle_hora :366-471, update_paos :473-499)."""
 from collections import Counter
 
 SITUATIONS = (
     "kyoku", "hora_total", "tsumo", "ron_single", "ron_double", "ron_triple", "chankan_ron", "ron_on_ankan", "rinshan_tsumo",
     "haitei_tsumo", "houtei_ron", "first_turn_win", "tenhou", "chiihou_position", "renhou_position", "double_riichi_declared",
-    "double_riichi_win", "ippatsu_win", "abort_kyuushu", "abort_four_winds", "abort_four_riichi", "abort_four_kans",
+    "double_riichi_win", "ippatsu_win", "abort_kyuushu", "abort_four_winds", "four_winds_broken", "abort_four_riichi", "abort_four_kans",
     "four_kans_one_seat_play_goes_on", "exhaustive_tenpai_0", "exhaustive_tenpai_1", "exhaustive_tenpai_2", "exhaustive_tenpai_3",
-    "exhaustive_tenpai_4", "nagashi_mangan_1", "nagashi_mangan_2", "nagashi_mangan_3", "nagashi_mangan_4", "pao_set_daisangen",
+    "exhaustive_tenpai_4", "nagashi_mangan_1", "nagashi_mangan_2", "nagashi_mangan_3", "nagashi_mangan_4", "nagashi_lost_to_call", "pao_set_daisangen",
     "pao_set_daisuushi", "pao_tsumo_paid", "pao_ron_split_paid", "pao_ron_from_liable", "win_32000_plus", "kan_dora_at_discard",
     "kan_dora_at_next_draw", "kan_dora_at_ankan", "consecutive_kans", "hanchan_ends_negative", "west_round_kyoku", "honba_3_plus",
     "kyotaku_2_plus",
@@ -108,6 +109,7 @@ class _Kyoku:
         self.called_on = [False] * 4       # a discard of the seat was taken by chi / pon / daiminkan
         self.any_call = False              # chi / pon / any kan so far (the first go-around is "uninterrupted" without one)
         self.first_discards = []
+        self.four_winds_due = False        # the last event was the fourth of four equal first wind discards, nothing called
         self.kans_by = [0] * 4
         self.accepted = [False] * 4
         self.reach_pending = None          # seat whose riichi awaits its discard
@@ -148,6 +150,11 @@ def census_by_kyoku(events):
             raise ValueError(f"{t} before any start_kyoku")
         if t != "hora" and k.hora_group:
             _close_hora_group(k, cnt)
+        if k.four_winds_due:
+            # the abort follows the fourth discard at once: no ron on it, no riichi accepted, no draw (board.rs:314-340, :587-600)
+            k.four_winds_due = False
+            if t != "ryukyoku":
+                cnt["mismatch:four_winds_not_aborted"] += 1
         if t == "tsumo":
             a = ev["actor"]
             k.draws += 1
@@ -167,6 +174,11 @@ def census_by_kyoku(events):
                 cnt["kan_dora_at_discard"] += 1
             if len(k.first_discards) < 4:
                 k.first_discards.append(p)
+                if len(k.first_discards) == 4 and _three_winds(k):
+                    if p == k.first_discards[0]:
+                        k.four_winds_due = True
+                    else:
+                        cnt["four_winds_broken"] += 1
             k.n_discards[a] += 1
             if p not in _YAOKYUU:
                 k.all_yaokyuu[a] = False
@@ -181,6 +193,8 @@ def census_by_kyoku(events):
             if k.after_fourth_kan_discard and max(k.kans_by) == 4:
                 cnt["four_kans_one_seat_play_goes_on"] += 1
                 k.after_fourth_kan_discard = False
+            if len(k.first_discards) == 3 and _three_winds(k):
+                cnt["four_winds_broken"] += 1
             for c in ev["consumed"]:
                 if t != "kakan":
                     k.hands[a][tile_id(c)] -= 1
@@ -234,6 +248,13 @@ def census_by_kyoku(events):
     if k is not None and k.hora_group:
         _close_hora_group(k, cnt)
     return out
+
+
+def _three_winds(k):
+    """The first three discards of the kyoku are one and the same wind and nothing was called or declared before or among them
+    (to be asked before the event at hand is booked: a call that answers the third discard still finds `any_call` unset)."""
+    f = k.first_discards[:3]
+    return len(f) == 3 and not k.any_call and f[0] == f[1] == f[2] and 27 <= f[0] <= 30
 
 
 def census(events):
@@ -331,6 +352,8 @@ def _ryukyoku(k, cnt, ev):
             cnt["mismatch:abort_deltas"] += 1
         return
     nagashi = [s for s in range(4) if k.all_yaokyuu[s] and not k.called_on[s]]
+    if any(k.all_yaokyuu[s] and k.called_on[s] for s in range(4)):
+        cnt["nagashi_lost_to_call"] += 1  # (such a seat is in no `nagashi` below: the payments wanted of it are those by tenpai)
     want = [0] * 4
     if nagashi:
         cnt[f"nagashi_mangan_{len(nagashi)}"] += 1

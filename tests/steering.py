@@ -12,6 +12,7 @@ import numpy as np
 
 _AKA = {4: 34, 13: 35, 22: 36}
 _YAOKYUU = (0, 8, 9, 17, 18, 26, 27, 28, 29, 30, 31, 32, 33)
+_WINDS = (27, 28, 29, 30)
 
 
 def _legal_discards(m):
@@ -126,6 +127,68 @@ def _terminal_discards(arena, m, g, seat, sn, cycle):
     return _fallback(m)
 
 
+def _first_go_around_discards(arena, g, seat):
+    """The discards of the other three seats as `seat` sees them (its own river is empty while it can still double-riichi)."""
+    ps = arena.player_state(g, seat)
+    return [(int(e) >> 1) & 63 for rel in (1, 2, 3) for e in ps.kawa(rel) if int(e) & 1]
+
+
+def _wind_discards(arena, m, g, seat, sn, cycle):
+    """`_terminal_discards`, but the first go-around follows the wind: a seat that holds the wind which every discard so far shows
+    discards it too, and the first seat opens with a wind (one it holds once before one it holds more often).  Kyuushu kyuuhai
+    is declared when `seat + cycle` is odd: both the abort and the kyoku played on from such a hand occur."""
+    if m[44] and (seat + cycle) & 1:
+        return 44
+    legal = _legal_discards(m)
+    # (`can_w_riichi`: the seat has not discarded and nobody has called or declared a kan, so the rivers are read four times
+    # per kyoku at the most)
+    if legal and sn["can_w_riichi"]:
+        seen = _first_go_around_discards(arena, g, seat)
+        if not seen:
+            winds = [t for t in _WINDS if t in legal]
+            if winds:
+                tehai = sn["tehai"]
+                return legal[_pick([t for t in winds if tehai[t] == 1] or winds, cycle + seat)]
+        elif len(set(seen)) == 1 and seen[0] in _WINDS and seen[0] in legal:
+            return legal[seen[0]]
+    return _terminal_discards(arena, m, g, seat, sn, cycle)
+
+
+def _calling_terminal_discards(arena, m, g, seat, sn, cycle):
+    """The seat opposite the dealer calls every pon and chi it can and discards its non-terminals first; the other three play
+    `_terminal_discards`.  A terminal-only river that loses a tile to the caller is no nagashi mangan at the exhaustive draw."""
+    if seat != ((int(arena.game_view(g)[10]) + 2) & 3):
+        return _terminal_discards(arena, m, g, seat, sn, cycle)
+    for a in (41, 38, 39, 40):
+        if m[a]:
+            return a
+    legal = _legal_discards(m)
+    if legal:
+        plain = [t for t in legal if t not in _YAOKYUU]
+        return legal[_pick(plain or list(legal), cycle + seat)]
+    return _fallback(m)
+
+
+def _first_go_around(arena, m, g, seat, sn, cycle):
+    """Wins in the first go-around: everybody wins when possible, nobody calls or declares riichi, and a seat that has not discarded
+    yet discards a tile that a seat still to come waits on (it looks at their hands in the oracle) if it holds one.  After its
+    first discard a seat plays shanten-lowering discards."""
+    if m[43]:
+        return 43
+    legal = _legal_discards(m)
+    if legal:
+        if sn["can_w_riichi"]:
+            fed = set()
+            for other in range(4):
+                o = arena.player_state(g, other).snapshot() if other != seat else None
+                if o is not None and o["can_w_riichi"]:
+                    fed.update(t for t in legal if o["waits"][t])
+            if fed:
+                return legal[_pick(fed, cycle + seat)]
+        return _shanten_discard(m, sn, cycle + seat)
+    return _fallback(m)
+
+
 def _honour_hoarding(arena, m, g, seat, sn, cycle):
     """The seat opposite the dealer keeps every honour and pons each one it can (and anything else once it has two melds).  The
     other three stay closed, declare riichi and discard honours on sight: first one the hoarder holds a pair of (they look at the
@@ -177,9 +240,25 @@ POLICIES = {
     "terminal_discards": _drive(_terminal_discards),
     "honour_hoarding": _drive(_honour_hoarding),
     "everybody_rons": _drive(_everybody_rons),
+    "wind_discards": _drive(_wind_discards),
+    "calling_terminal_discards": _drive(_calling_terminal_discards),
+    "first_go_around": _drive(_first_go_around),
 }
-# policies under which nobody wins by choice: their games need not end, a table runs to its recorded stop cycle
-NEVER_ENDING = ("kan_seeking", "closed_riichi_no_win", "terminal_discards")
+# policies whose tables run to their recorded stop cycle and no further: under the first five nobody wins by choice and the games
+# need not end; `first_go_around` is searched over the first cycles of very many hanchan, of which nothing more is known
+NEVER_ENDING = ("kan_seeking", "closed_riichi_no_win", "terminal_discards", "wind_discards", "calling_terminal_discards",
+                "first_go_around")
+
+
+def _non_dealer_tenpai_at_deal(arena, g):
+    oya = int(arena.game_view(g)[10])
+    return any(arena.player_state(g, s).snapshot()["shanten"] == 0 for s in range(4) if s != oya)
+
+
+# policy -> `(arena, table) -> bool`, asked after the first poll: can the hanchan's first kyoku reach what the policy was written
+# for?  tools/find_situation_seeds.py plays on only the tables that can (a win by a non-dealer in the first go-around needs a hand
+# that is tenpai as dealt: one deal in some thousand).  A test replays a seed whatever this says.
+DEAL_FILTER = {"first_go_around": _non_dealer_tenpai_at_deal}
 
 
 def play_oracle(oracle, seeds, policy, deal_algo=0, max_cycles=6000, version=3):

@@ -148,15 +148,17 @@ def test_exhaustive_draw_by_tenpai_seats_tells_none_from_all():
     assert C.census(run(1, [1500, 1500, -1500, -1500]))["mismatch:exhaustive_deltas"] == 1
 
 
-def test_nagashi_mangan_by_number_of_seats():
-    def run(yao_seats, deltas):
-        ev = [sk(oya=1)]
-        for i in range(70):
-            s = (1 + i) % 4
-            p = "9p" if s in yao_seats else "5m"
-            ev += [ts(s, p), da(s, p)]
-        return ev + [ryu(deltas), END]
+def _nagashi_run(yao_seats, deltas):
+    ev = [sk(oya=1)]
+    for i in range(70):
+        s = (1 + i) % 4
+        p = "9p" if s in yao_seats else "5m"
+        ev += [ts(s, p), da(s, p)]
+    return ev + [ryu(deltas), END]
 
+
+def test_nagashi_mangan_by_number_of_seats():
+    run = _nagashi_run
     has(run({1}, [-4000, 12000, -4000, -4000]), nagashi_mangan_1=1)
     has(run({2}, [-2000, -4000, 8000, -2000]), nagashi_mangan_1=1)
     has(run({0, 2}, [6000, -8000, 6000, -4000]), nagashi_mangan_2=1, nagashi_mangan_1=0)
@@ -166,6 +168,56 @@ def test_nagashi_mangan_by_number_of_seats():
     ev[at - 1], ev[at] = ts(2, "E"), da(2, "E")
     ev[at + 1:at + 1] = [pon(0, 2, "E"), da(0, "1m")]
     has(ev, nagashi_mangan_1=0, exhaustive_tenpai_0=1)
+
+
+def test_four_winds_aborted_broken_and_not_aborted():
+    three = [sk(), ts(0), da(0, "W"), ts(1), da(1, "W"), ts(2), da(2, "W"), ts(3)]
+    has(three + [da(3, "W"), ryu(), END], abort_four_winds=1, four_winds_broken=0, abort_kyuushu=0)
+    # the fourth discard differs (another wind included), or a call or a concealed kan comes first: play goes on
+    has(three + [da(3, "N"), ts(0), da(0)], four_winds_broken=1, abort_four_winds=0)
+    has(three + [da(3, "1m"), ts(0), da(0)], four_winds_broken=1)
+    has(three[:-1] + [pon(0, 2, "W"), da(0), ts(1), da(1)], four_winds_broken=1)
+    has(three[:-1] + [ts(3, "1m"), kan("ankan", 3, "1m"), DORA, ts(3), da(3, "W"), ts(0), da(0)], four_winds_broken=1, abort_four_winds=0)
+    # not three of a kind, not winds, or a call before the third: nothing to break
+    has([sk(), ts(0), da(0, "W"), ts(1), da(1, "N"), ts(2), da(2, "W"), ts(3), da(3, "W"), ts(0), da(0)], four_winds_broken=0)
+    has([sk(), ts(0), da(0, "P"), ts(1), da(1, "P"), ts(2), da(2, "P"), ts(3), da(3, "P"), ts(0), da(0)], four_winds_broken=0)
+    has([sk(), ts(0), da(0, "W"), ts(1), da(1, "W"), pon(3, 1, "W"), da(3, "W"), ts(0), da(0, "W"), ts(1), da(1)], four_winds_broken=0)
+    # four equal winds and the game goes on, by a draw, a ron or an accepted riichi: the log contradicts the rule
+    for after in ([ts(0), da(0)], [hora(0, 3, [1000, 0, 0, -1000]), END], [{"type": "reach_accepted", "actor": 3}, ts(0)]):
+        got = C.census(three + [da(3, "W")] + after)
+        assert got["mismatch:four_winds_not_aborted"] == 1 and got["abort_four_winds"] == 0, got
+    assert not [k for k in C.census(three + [da(3, "W")]) if k.startswith("mismatch:")]  # (a log that stops there says nothing)
+
+
+def test_the_two_early_aborts_are_told_apart_by_the_events_alone():
+    # a `ryukyoku` carries deltas and nothing else: after a draw it is the nine terminals, after the fourth wind the four winds
+    kyuushu = [sk(tehais=[ANY, KYUUSHU, ANY, ANY]), ts(0), da(0, "W"), ts(1, "N"), ryu(), END]
+    has(kyuushu, abort_kyuushu=1, abort_four_winds=0)
+    winds = [sk(tehais=[KYUUSHU] * 4), ts(0), da(0, "E"), ts(1), da(1, "E"), ts(2), da(2, "E"), ts(3), da(3, "E"), ryu(), END]
+    has(winds, abort_four_winds=1, abort_kyuushu=0)
+    # nine terminals declared by a hand that does not hold them, or after a call
+    assert C.census([sk(), ts(0, "N"), ryu(), END])["mismatch:kyuushu"] == 1
+    assert C.census([sk(tehais=[ANY, ANY, KYUUSHU, ANY]), ts(0), da(0, "P"), pon(1, 0, "P"), da(1), ts(2, "N"), ryu(), END])["mismatch:kyuushu"] == 1
+
+
+def test_nagashi_lost_to_a_call_is_paid_by_tenpai():
+    def run(deltas, tehais=None):
+        ev = [sk(oya=1, tehais=tehais)]
+        for i in range(70):
+            s = (1 + i) % 4
+            p = "9p" if s == 2 else "5m"
+            ev += [ts(s, p), da(s, p)]
+        at = next(i for i, e in enumerate(ev) if e["type"] == "dahai" and e["actor"] == 2)
+        ev[at - 1], ev[at] = ts(2, "E"), da(2, "E")
+        ev[at + 1:at + 1] = [pon(0, 2, "E"), da(0, "1m")]
+        return ev + [ryu(deltas), END]
+
+    has(run([0, 0, 0, 0]), nagashi_lost_to_call=1, nagashi_mangan_1=0, exhaustive_tenpai_0=1)
+    has(run([-1000, -1000, 3000, -1000], tehais=[ANY, ANY, TENPAI, ANY]), nagashi_lost_to_call=1, exhaustive_tenpai_1=1)
+    # the mangan paid all the same
+    assert C.census(run([-2000, -4000, 8000, -2000]))["mismatch:exhaustive_deltas"] == 1
+    # terminals only, nothing called: a nagashi mangan, nothing lost
+    has(_nagashi_run({2}, [-2000, -4000, 8000, -2000]), nagashi_mangan_1=1, nagashi_lost_to_call=0)
 
 
 def _daisangen(last="pon"):

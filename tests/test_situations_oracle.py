@@ -17,7 +17,7 @@ def test_fixture_covers_every_target_and_both_deal_algorithms():
     assert {e["deal_algo"] for e in doc["entries"]} == {"rand08", "rand09"}
     # (rare even under steering: the search of `kyoku_searched` kyoku holds fewer than eight tables of them)
     rare = ("pao_ron_split_paid", "pao_tsumo_paid", "pao_set_daisuushi", "ron_triple", "ron_on_ankan", "tenhou", "first_turn_win",
-            "four_kans_one_seat_play_goes_on", "nagashi_mangan_2")
+            "four_kans_one_seat_play_goes_on", "nagashi_mangan_2", "pao_ron_from_liable")
     for e in doc["entries"]:
         assert e["count"] == len(e["tables"]) >= (2 if e["situation"] in rare else 8), e["situation"]
         assert e["policy"] in steering.POLICIES
