@@ -176,8 +176,10 @@ int mj_encode_timing(MjPool* pool, int enable, double* total_ms_out, int64_t* la
 int mj_sp_timing(MjPool* pool, double* total_ms_out, int64_t* launches_out);
 /* Cumulative phase timers of mj_k_sp since the pool was created (workgroup wall-clock ticks at 100 MHz, summed over all
  * workgroups): out[0] hash/pool overflows, [1] rows, [2] set-up, [3] expansion, [4] level 0 (probe + scoring + sum),
- * [5] evaluation of levels > 0, [6] writing the rows, [7] states visited.  Measurement only (bench.py `sp_phases`). */
-int mj_sp_phase_ticks(MjPool* pool, uint64_t* out8, void* stream);
+ * [5] evaluation of levels > 0, [6] writing the rows, [7] states visited, [8] rows with as many draws left as their shanten number
+ * (their tenpai level is neither built nor evaluated, so [7] holds no level-0 state of theirs).  Measurement only (bench.py
+ * `sp_phases`). */
+int mj_sp_phase_ticks(MjPool* pool, uint64_t* out9, void* stream);
 /* Small-pool schedule of the SP kernel (round 6).  The reference spreads the decisions of a batch over every core and pins nothing
  * (agent/mortal.rs:252-287: rayon par_iter over the batch's states); here a decision row is pinned to one 256-thread workgroup of
  * mj_k_sp, and with few rows per launch the launch lasts as long as its heaviest row.  With the schedule on, a workgroup that finds a

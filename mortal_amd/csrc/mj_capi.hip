@@ -774,6 +774,7 @@ static int sp_setup(MjPool* P, int agent, float* obs, hipStream_t s) {
         SpWork& W = R.work.get()[g];
         HIP_OK(hipMemsetAsync(W.tag, 0, sizeof(W.tag), s));  // empty hash sets ...
         HIP_OK(hipMemsetAsync(&W.epoch, 0, sizeof(W.epoch) + sizeof(W.pad_), s));  // ... at epoch 0
+        HIP_OK(hipMemsetAsync(&W.node[SP_ZERO_SLOT], 0, sizeof(SpNode), s));  // the child of a dead tenpai level's draw entries: zeros, never written
     }
     if (R.queue.alloc(SP_Q_WORDS)) return -1;
     if (R.spare) {
@@ -1049,12 +1050,12 @@ int mj_counters(MjPool* P, uint64_t out[8], void* stream) {
         const unsigned long long* pass = e2 + SP_ERR_PASS;  // (seven words: SpCtx::pt[0..6])
         if (P->knobs.sp_prof)
             fprintf(stderr, "[sp prof] rows %llu setup %llu expand %llu evalL0 %llu evalL>0 %llu encode %llu states %llu (wall_clock64 ticks, 100 MHz) | "
-                    "expand passes: probes %llu lists+V %llu td-probes %llu layout %llu inserts %llu; items %llu expanded %llu edges %llu l0-entries %llu; level-0 probe %llu scoring %llu; workgroup lifetimes: sum %llu max %llu queue pops %llu hash resets %llu; eval wavefront time %llu; shader clock %.0f MHz (s_memtime cycles %llu over the lifetimes)\n",
+                    "expand passes: probes %llu lists+V %llu td-probes %llu layout %llu inserts %llu; items %llu expanded %llu edges %llu l0-entries %llu; level-0 probe %llu scoring %llu; workgroup lifetimes: sum %llu max %llu queue pops %llu hash resets %llu; eval wavefront time %llu; shader clock %.0f MHz (s_memtime cycles %llu over the lifetimes); dead-leaf rows %llu\n",
                     e2[SP_ERR_ROWS], e2[SP_ERR_T_SETUP], e2[SP_ERR_T_EXPAND], e2[SP_ERR_T_EVAL0], e2[SP_ERR_T_EVAL], e2[SP_ERR_T_WRITE], e2[SP_ERR_STATES],
                     pass[0], pass[1], pass[2], pass[3], pass[4], pass[5], pass[6], e2[SP_ERR_EDGES], e2[SP_ERR_L0_ITEMS],
                     e2[SP_ERR_T_L0_PROBE], e2[SP_ERR_T_L0_SCORE], e2[SP_ERR_WG_LIFE], e2[SP_ERR_WG_LIFE_MAX], e2[SP_ERR_T_POP], e2[SP_ERR_T_RESET],
                     e2[SP_ERR_T_EVAL_WAVE], e2[SP_ERR_WG_LIFE] ? 100.0 * (double)e2[SP_ERR_WG_CLOCK] / (double)e2[SP_ERR_WG_LIFE] : 0.0,
-                    e2[SP_ERR_WG_CLOCK]);
+                    e2[SP_ERR_WG_CLOCK], e2[SP_ERR_DEAD_LEAF]);
     }
     return 0;
 }
@@ -1078,14 +1079,15 @@ void mj_emu_fail_nth(int alloc, int sync) { emu::R().fail_alloc_in = alloc, emu:
 #endif
 #endif
 
-int mj_sp_phase_ticks(MjPool* P, uint64_t out[8], void* stream) {
+int mj_sp_phase_ticks(MjPool* P, uint64_t out[9], void* stream) {
     if (!P) return fail("null pool");
-    for (int i = 0; i < 8; i++) out[i] = 0;
+    for (int i = 0; i < 9; i++) out[i] = 0;
     if (!P->sp.err) return 0;  // no obs-v4 encode has run yet
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    unsigned long long e2[8];  // SP_ERR_OVERFLOW .. SP_ERR_STATES
+    unsigned long long e2[SP_ERR_WORDS];
     HIP_OK(hipMemcpy(e2, P->sp.err.get(), sizeof e2, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 8; i++) out[i] = e2[i];
+    for (int i = 0; i < 8; i++) out[i] = e2[i];  // SP_ERR_OVERFLOW .. SP_ERR_STATES
+    out[8] = e2[SP_ERR_DEAD_LEAF];
     return 0;
 }
 

@@ -69,7 +69,8 @@
 #endif
 #define SP_SET_SLOTS (2 * SP_SET_BUCKETS)  // node slots [0, SP_SET_SLOTS) = the ways of the LDS set; a state of the HBM table: SP_SET_SLOTS + position
 #define SP_NODES (SP_CAP + SP_SET_SLOTS)
-static_assert((SP_SET_BUCKETS & (SP_SET_BUCKETS - 1)) == 0 && SP_SET_BUCKETS >= 1 && SP_NODES <= (1 << 15), "slots are 15-bit fields");
+#define SP_ZERO_SLOT SP_NODES    // one node past the states' own: all zero, never written (the child of every draw entry of a dead tenpai level, sp_expand_dead_chunk)
+static_assert((SP_SET_BUCKETS & (SP_SET_BUCKETS - 1)) == 0 && SP_SET_BUCKETS >= 1 && SP_ZERO_SLOT < (1 << 15), "slots are 15-bit fields");
 #ifndef SP_TAIL_BATCH
 #define SP_TAIL_BATCH 4         // rows per pop in the tail of the queue (rows without a state graph, one row per wavefront)
 #endif
@@ -126,7 +127,8 @@ struct alignas(16) SpF4 { float x, y, z, w; };
 #define SP_HANDOFF_WORDS 1024   // >= sizeof(SpHandoff) / 4 (static_assert below)
 struct alignas(128) SpWork {   // per-workgroup scratch in HBM (persistent workgroups), 8.6 MB
     u64 tag[SP_CAP];           // state id | row epoch << 42 | 1 << 63; a tag of another epoch (or 0) is an EMPTY slot
-    SpNode node[SP_NODES];     // by slot: [0, SP_SET_SLOTS) the ways of the LDS set (mj_k_sp), SP_SET_SLOTS + position in tag[]
+    SpNode node[SP_NODES + 1]; // by slot: [0, SP_SET_SLOTS) the ways of the LDS set (mj_k_sp), SP_SET_SLOTS + position in tag[]; SP_ZERO_SLOT: zeroed with the
+                               // area (sp_setup), nobody's state
     SpKeys keys[SP_CAP];       // by list index
     SpHdr hdr[SP_CAP];         // by list index
     u32 list[SP_CAP];          // slots grouped by level: level L occupies [lvl_begin[L], lvl_end[L])
@@ -197,7 +199,7 @@ enum SpErrWord {
     SP_ERR_T_EVAL0 = 4,       //   level 0 (probe + scoring + sum)
     SP_ERR_T_EVAL = 5,        //   evaluation of levels > 0
     SP_ERR_T_WRITE = 6,       //   writing the row
-    SP_ERR_STATES = 7,        // states visited
+    SP_ERR_STATES = 7,        // states visited (a row of SP_ERR_DEAD_LEAF has no level-0 states: this word, the edges and the level-0 entries count less for it)
     SP_ERR_PASS = 8,          // [8..14] expansion pass timers / counters (SpCtx::pt[0..6], MJ_SP_PROF)
     SP_ERR_EDGES = 15,        // child-list entries (edges of the state graphs)
     SP_ERR_L0_ITEMS = 16,     // level-0 draw entries scored
@@ -217,7 +219,9 @@ enum SpErrWord {
     SP_ERR_DUMP_NARROW = 29,  //   last narrow / ...
     SP_ERR_DUMP_WIDE = 30,    //   ... wide workgroup out of them,
     SP_ERR_DUMP_TAIL = 31,    //   end of the queue's tail
-    SP_ERR_WORDS = 32
+    SP_ERR_DEAD_LEAF = 32,    // rows with as many draws left as their shanten number (the last draw only reaches tenpai): level 1 expanded by
+                              // sp_expand_dead_chunk, level 0 neither built nor evaluated
+    SP_ERR_WORDS = 33
 };
 
 // algo/data/uradora_prob_table.txt (values restated; calc.rs:17)
@@ -354,6 +358,17 @@ template <class Bp> __device__ __forceinline__ SpF3 sp_ld3(Bp base, u32 byte_off
     const SP_HBM SpF3* p = reinterpret_cast<const SP_HBM SpF3*>(reinterpret_cast<const SP_HBM char*>(base) + (unsigned long long)byte_off);
     SpF3 r;
     r.x = p->x; r.y = p->y; r.z = p->z;
+    return r;
+#endif
+}
+struct SpF2 { float x, y; };
+template <class Bp> __device__ __forceinline__ SpF2 sp_ld2(Bp base, u32 byte_off) {  // one 8-byte load
+#ifdef MJ_EMU
+    return *reinterpret_cast<const SpF2*>(reinterpret_cast<const char*>(base) + byte_off);
+#else
+    const SP_HBM SpF2* p = reinterpret_cast<const SP_HBM SpF2*>(reinterpret_cast<const SP_HBM char*>(base) + (unsigned long long)byte_off);
+    SpF2 r;
+    r.x = p->x; r.y = p->y;
     return r;
 #endif
 }
@@ -1070,6 +1085,14 @@ __device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, 
                                    (int)C->cnt[s][2] + (yao && hc == 1), (int)C->cnt[s][3] + (yao && hc == 0), sp_count_sets_add(cs, t, hc));
             }
             kept &= ~(1ull << t);  // d == t gives the state itself back
+#ifdef MJ_EMU
+            // sp_expand_dead_chunk writes one entry per draw entry without looking for the discards, so every required draw of a 1-shanten
+            // state must have a keeping discard other than the drawn tile, or the two paths would disagree about n_ent.  It has one: drawing
+            // t makes the 14 tiles tenpai, so some discard keeps tenpai, and discarding t gives the 1-shanten state back, so that discard is
+            // not t.  This only guards the table code against the argument (the flag is the row's overflow flag: a lock-step that trips it
+            // fails, whichever reason raised it).
+            if (L == 1 && kept == 0ull) X->overflow = 1;
+#endif
             C->kept[tid] = kept;
         }
         if (prof) tp2 = wall_clock64();
@@ -1292,6 +1315,60 @@ __device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, 
         atomicAdd(&X->pt[4], (unsigned long long)acc_ins);       // P4 inserts
         atomicAdd(&X->pt[5], (unsigned long long)n_items_total); // draw items
         atomicAdd(&X->pt[6], (unsigned long long)n);             // states expanded
+    }
+}
+
+// Level 1 of a row with as many draws left as its shanten number (sp_kernel_body: leaf_dead).  Its tenpai states are reached with no
+// draw left: their values are all zero and nobody reads them -- the single lane of a level-1 state (turn T - 1) adds prob x next[T], a
+// turn that does not exist (the parked row's zero fill), and its tenpai sum is the probabilities alone (sp_eval_wave<.., 1>).  So the
+// level below is never built: no keep-discard probe (P2), no insert, no new state.  The child list keeps its shape -- one entry per
+// draw entry (tile ascending, plain before red) with the entry's copy count, SP_ENT_LAST, and the all-zero node SP_ZERO_SLOT as its
+// child -- and the header what sp_expand_chunk writes (every required draw has a keeping discard: checked there under MJ_EMU), so the
+// evaluation runs unchanged.  Out of line and for these rows only: the expansion of every other row compiles as before.
+__device__ __noinline__ void sp_expand_dead_chunk(SpWork* W, SpCtx* X, SpChunk* C, int first, int n) {
+    SP_ASSUME_LDS(X);
+    SP_ASSUME_LDS(C);
+    SP_HBM SpWork* const Wg = (SP_HBM SpWork*)W;
+    const SpTabG TG = sp_tab_g(*SP_OPQ_PTR(1, &c_sp_tab));
+    const bool prof = X->prof != nullptr;
+    const long long tq0 = prof ? wall_clock64() : 0;
+    sp_chunk_probe(Wg, X, C, TG, first, n, 1);
+    const int s = threadIdx.x & (SP_NT - 1);
+    if (s < n) {
+        const SpState S = sp_chunk_state(C, s);
+        const u64 req = C->req[s];
+        int total = 0, sumreq = 0;
+        for (u64 rest = req; rest; rest &= rest - 1) {
+            const int t = __ffsll((long long)rest) - 1, wc = S.w.get(t);
+            total += sp_aka_in_wall(S, t) && wc >= 2 ? 2 : 1;
+            sumreq += wc;
+        }
+        int base = 0;
+        if (total) {
+            base = atomicAdd(&X->n_pool, total);
+            if (base + total > SP_POOL) { X->overflow = 1; base = SP_POOL; total = 0; }
+        }
+        int e = 0;
+        for (u64 rest = req; rest; rest &= rest - 1) {
+            const int t = __ffsll((long long)rest) - 1, wc = S.w.get(t);
+            const bool aka = sp_aka_in_wall(S, t);
+            for (int variant = 0; variant < 2; variant++) {  // plain (all copies but the red one) if any, then the red five
+                if (variant == 0 ? (aka && wc < 2) : !aka) continue;
+                const int count = !aka ? wc : variant == 0 ? wc - 1 : 1;
+                if (e < total && base + e < SP_POOL) Wg->pool[base + e] = (u32)SP_ZERO_SLOT | SP_ENT_LAST | ((u32)count << 25);
+                e++;
+            }
+        }
+        SP_HBM SpHdr& hd = Wg->hdr[first + s];
+        hd.child_off = total ? (u32)min(base, SP_POOL - 1) : 0u;
+        hd.n_ch = (unsigned short)total;
+        hd.sumreq = (u8)(sumreq & 0xFF);
+        hd.n_ent = (u8)min(total, 255);
+    }
+    mj_team_sync<SP_NT>();
+    if (prof && s == 0) {
+        atomicAdd(&X->pt[0], (unsigned long long)(wall_clock64() - tq0));  // (the whole call: probes and lists)
+        atomicAdd(&X->pt[6], (unsigned long long)n);
     }
 }
 
@@ -1518,7 +1595,17 @@ __device__ SP_ATTR_EVAL void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
     auto ld_hdr = [&](u32 el) -> u64 { return sp_ld<unsigned long long>(hdrB, 16u * SP_EL_IDX(el)); };
     auto ld_m = [&](u64 hdr) -> float { return sp_ld<float>(nt_rows, 4u * ((u32)min((int)((hdr >> 48) & 0xFF), SP_NT_ROWS - 1) * SP_NT_STRIDE + (u32)ln)); };
     auto ld_ent = [&](u32 at) -> u32 { return sp_ld<u32>(poolB, 4u * min(at, (u32)(SP_POOL - 1))); };
-    auto ld_val = [&](u32 ent) -> SpF3 { return sp_ld3(nodeB, SP_ENT_SLOT(ent) * (u32)sizeof(SpNode) + val_ln); };  // one 12-byte load
+    // one 12-byte load; level 1 never uses its children's tenpai value (its tenpai sum is the probabilities alone: `acc_t += prob` below),
+    // so it loads the other two (8 bytes) and neither folds nor parks the first
+    auto ld_val = [&](u32 ent) -> SpF3 {
+        const u32 at = SP_ENT_SLOT(ent) * (u32)sizeof(SpNode) + val_ln;
+        if constexpr (LK == 1) {
+            const SpF2 p = sp_ld2(nodeB, at + 4u);
+            return SpF3{0.f, p.x, p.y};
+        } else {
+            return sp_ld3(nodeB, at);
+        }
+    };
     mj_team_sync<64>();
 
     // the pipeline: state 0 = current, 1 = next (header, first entries and not_tsumo value loaded), 2 = header loaded, 3 = slot
@@ -1567,7 +1654,7 @@ __device__ SP_ATTR_EVAL void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
             if (valid && !bad && lane_in_team > 0 && ((unsigned)sp_f2i(v[q].z) >> 22)) X->overflow = 1;
 #endif
             const bool better = valid && !bad && pack > max_pack;
-            nx_t = better ? v[q].x : nx_t;
+            if constexpr (LK != 1) nx_t = better ? v[q].x : nx_t;
             nx_w = better ? v[q].y : nx_w;
             nx_e = better ? v[q].z : nx_e;
             max_pack = better ? pack : max_pack;
@@ -1575,7 +1662,7 @@ __device__ SP_ATTR_EVAL void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
                 const u32 cnt = SP_ENT_COUNT(e);  // 1..4 copies of the drawn tile
                 const float tpc = cnt <= 1 ? tp0 : cnt == 2 ? tp1 : cnt == 3 ? tp2 : tp3;
                 float* row = row0 + koff;
-                row[0] = nx_t;
+                if constexpr (LK != 1) row[0] = nx_t;  // (level 1: stays the zero fill, nobody reads it)
                 row[1] = nx_w;
                 row[2] = nx_e;
                 row[7] = tpc * m_raw;  // A[ln], read with row ln + 1
@@ -1991,6 +2078,7 @@ __device__ __forceinline__ SpRowInfo sp_row_front(RowsP rows, SnapP snap, SpWork
             X.n_left = n_left;
             X.n_list = 0;
             X.n_pool = 0;
+            X.n_items = 0;  // (a row without level 0 never sets it)
             X.overflow = 0;
             X.prof = prof;
             for (int k = 0; k < 8; k++) X.pt[k] = 0;
@@ -2265,8 +2353,8 @@ template <int NT, bool WIDE, bool PROMO>
 __device__ __forceinline__ void sp_kernel_body(SpParams P) {
     __shared__ SpCtx X;
     __shared__ int s_row, s_k;
-    __shared__ unsigned long long s_stat[SP_ERR_STATS];  // this workgroup's share of SpParams::err, flushed once (see sp_light_row)
-    if (threadIdx.x < SP_ERR_STATS) s_stat[threadIdx.x] = 0ull;
+    __shared__ unsigned long long s_stat[SP_ERR_STATS + 1];  // this workgroup's share of SpParams::err, flushed once (see sp_light_row); [SP_ERR_STATS]: SP_ERR_DEAD_LEAF
+    if (threadIdx.x <= SP_ERR_STATS) s_stat[threadIdx.x] = 0ull;
     __shared__ typename SpLds<NT>::Teams s_tm;
     // the expansion's table in LDS (sp_expand_chunk).  A parked row is finished by another workgroup and LDS does not travel, so only
     // mj_k_sp, which neither parks rows nor takes them over, keeps states there; the other two kernels keep the child cache.
@@ -2396,6 +2484,10 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         const int cur_shanten = R.cur_shanten, n_cand = R.n_cand, T = R.T;
         const bool with_probs = R.with_probs, can_discard = R.can_discard;
         const SpState root = R.root;
+        // as many draws left as the shanten number: the last draw only reaches tenpai, so level 0 is dead (sp_expand_dead_chunk).  Every draw
+        // lowers the shanten number by exactly one here (no tegawari, no shanten-down), so a level-L state sits exactly cur_shanten - L draws
+        // below the roots.  leaf_dead = with_probs && cur_shanten >= 1 && T == cur_shanten is spelled out at its three uses, from values that are
+        // live anyway; a parked row's second workgroup derives it from the hand-off's R like the first.
         // fewer draws left than the shanten number: tenpai / win / EV are exactly zero for every candidate (reaching tenpai
         // takes cur_shanten draws), so the state graph need not be built at all
         if (!promoted) {
@@ -2490,8 +2582,13 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                 // every wavefront its own chunks; a level too small for four full chunks is split four ways (a chunk pass costs
                 // the same for 4 states as for 16, so idle wavefronts are the only thing to lose)
                 const int ns = min(SP_NS, max(1, (e - b + NT / SP_NT - 1) / (NT / SP_NT)));
-                for (int c0 = b + ns * (tid / SP_NT); c0 < e; c0 += ns * (NT / SP_NT))
-                    sp_expand_chunk<LDS_SET>(W, &X, &s_tm.wchunk[tid / SP_NT], c0, min(ns, e - c0), lv);
+                if (__builtin_expect(lv == 1 && T == cur_shanten, 0)) {  // leaf_dead (level 0 stays empty: lvl_begin[0] == lvl_end[0] below)
+                    for (int c0 = b + ns * (tid / SP_NT); c0 < e; c0 += ns * (NT / SP_NT))
+                        sp_expand_dead_chunk(W, &X, &s_tm.wchunk[tid / SP_NT], c0, min(ns, e - c0));
+                } else {
+                    for (int c0 = b + ns * (tid / SP_NT); c0 < e; c0 += ns * (NT / SP_NT))
+                        sp_expand_chunk<LDS_SET>(W, &X, &s_tm.wchunk[tid / SP_NT], c0, min(ns, e - c0), lv);
+                }
                 __syncthreads();
                 if (tid == 0) {
                     X.lvl_begin[lv - 1] = e;
@@ -2500,12 +2597,13 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                 __syncthreads();
             }
             t_2 = wall_clock64();
+            t_3 = t_2;  // (a row without level 0)
 #ifdef MJ_EMU
             if (tid == 0 && !parked) sp_emu_check_unique(W, &X);  // (its verdict is read after the row's last barrier)
 #endif
             // evaluate bottom-up
             if (!parked)
-            for (int lv = 0; lv <= cur_shanten; lv++) {
+            for (int lv = (cur_shanten >= 1 && T == cur_shanten) ? 1 : 0; lv <= cur_shanten; lv++) {  // (leaf_dead: no probe, no scoring, no sort, no sums)
                 const int b = X.lvl_begin[lv], e = X.lvl_end[lv];
                 if (lv == 0) {
                     if (tid == 0) X.n_items = 0;
@@ -2569,6 +2667,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         if (tid == 0) {
             long long t_5 = wall_clock64();
             if (!parked) s_stat[SP_ERR_ROWS] += 1ull;
+            if (!parked && with_probs && cur_shanten >= 1 && T == cur_shanten) s_stat[SP_ERR_STATS] += 1ull;  // leaf_dead
             s_stat[SP_ERR_T_SETUP] += (unsigned long long)(t_1 - t_0);
             if (with_probs) {
                 s_stat[SP_ERR_T_EXPAND] += (unsigned long long)(t_2 - t_1);
@@ -2633,6 +2732,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         atomicMax(&P.err[WIDE ? SP_ERR_DUMP_WIDE : SP_ERR_DUMP_NARROW], (unsigned long long)wall_clock64());
     }
     if (tid < SP_ERR_STATS && tid != SP_ERR_WG_LIFE_MAX && s_stat[tid]) atomicAdd(&P.err[tid], s_stat[tid]);  // the workgroup's statistics, once
+    if (tid == SP_ERR_STATS && s_stat[tid]) atomicAdd(&P.err[SP_ERR_DEAD_LEAF], s_stat[tid]);
     // ---- the tail of the queue: every wavefront takes its own rows (set-up + encoder only, no workgroup barrier any more)
     // The tail has its own head word (another 128-byte line than the heavy rows' head) and is popped SP_TAIL_BATCH rows at a time:
     // ~46 k light rows per launch against 4,096 wavefronts that need ~10 us per row ask for ~400 pops per microsecond, and one word

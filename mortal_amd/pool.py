@@ -468,9 +468,9 @@ class TablePool:
 
     def sp_phase_ticks(self):
         """Cumulative mj_k_sp phase timers (workgroup ticks, 100 MHz) and counts since the pool was created."""
-        out = (C.c_uint64 * 8)()
+        out = (C.c_uint64 * 9)()
         check(self._L.mj_sp_phase_ticks(self.h, out, self._stream()))
-        return dict(zip(("overflow", "rows", "setup", "expand", "level0", "eval", "write", "states"), (int(x) for x in out)))
+        return dict(zip(("overflow", "rows", "setup", "expand", "level0", "eval", "write", "states", "dead_leaf_rows"), (int(x) for x in out)))
 
     def set_sp_schedule(self, mode=-2, max_rows=0, wide_grid=0, min_level1=0, min_level2=0):
         """Small-pool schedule of the SP kernel (include/mortal_amd.h mj_pool_set_sp_schedule): mode -1 auto / 0 never / 1 always."""
