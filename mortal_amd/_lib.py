@@ -5,107 +5,132 @@ There is no fallback: if the shared library is missing or fails to load, importi
 import ctypes as C
 import os
 
+# torch ships its own libamdhip64; it must be in the process before libmortal_amd.so is opened, otherwise the
+# system copy gets bound first and the two HIP runtimes disagree about the visible devices
+import torch
+
 _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MORTAL_AMD_LIB") or os.path.join(_DIR, "libmortal_amd.so")  # env override: A/B builds
 
-# Every symbol include/mortal_amd.h declares (tests/test_host.py checks the library exports all of them).
-SYMBOLS = [
-    "mj_last_error", "mj_abi_version", "mj_tables_upload", "mj_pool_create", "mj_pool_destroy", "mj_pool_reset",
-    "mj_pool_configure", "mj_pool_set_refill", "mj_pool_set_start_stagger", "mj_table_apply_event", "mj_table_mark_row", "mj_table_query", "mj_replay_load", "mj_replay_step", "mj_replay_meta", "mj_pool_enable_log", "mj_log_lengths", "mj_log_read", "mj_step", "mj_step_q", "mj_step_ev", "mj_rows_count", "mj_rows_dev", "mj_encode",
-    "mj_encode_oracle", "mj_oracle_obs_rows", "mj_encode_timing", "mj_sp_timing", "mj_sp_phase_ticks", "mj_pool_set_sp_schedule", "mj_sp_schedule_stats", "mj_random_policy", "mj_greedy_policy", "mj_counters", "mj_results", "mj_pool_first_error", "mj_debug_table",
-    "mj_debug_table_size", "mj_debug_layout", "mj_obs_rows", "mj_algo_query", "mj_stat_logs", "mj_pool_stat",
-    "mj_replay_load_pool", "mj_grp_logs", "mj_pool_grp", "mj_augment_logs",
-    "mj_pool_enable_harvest", "mj_harvest_pending", "mj_harvest_take", "mj_harvest_destroy", "mj_harvest_info", "mj_harvest_games",
-    "mj_harvest_read", "mj_harvest_stat", "mj_harvest_grp", "mj_replay_load_harvest",
-]
+_vp, _i32, _u32, _u64, _sz, _str = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_char_p
+# name: (restype, argtypes) of every symbol include/mortal_amd.h declares (tests/test_host.py checks the names and the number
+# of parameters against the header, and that the library exports all of them)
+PROTOTYPES = {
+    "mj_last_error": (_str, []),
+    "mj_abi_version": (_i32, []),
+    "mj_tables_upload": (_i32, [_vp, _sz]),
+    "mj_pool_create": (_vp, [_i32, _i32, _i32, _i32]),
+    "mj_pool_destroy": (None, [_vp]),
+    "mj_pool_reset": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32]),
+    "mj_pool_configure": (_i32, [_vp, _i32, _i32, _i32, _i32]),
+    "mj_pool_set_refill": (_i32, [_vp, _u64]),
+    "mj_pool_set_start_stagger": (_i32, [_vp, _u32, _vp]),
+    "mj_table_apply_event": (_i32, [_vp, _i32, _vp, _i32, _vp]),
+    "mj_table_mark_row": (_i32, [_vp, _i32, _i32, _i32, _vp]),
+    "mj_table_query": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mj_replay_load": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "mj_replay_step": (_i32, [_vp, _vp]),
+    "mj_replay_meta": (_i32, [_vp, _vp, _vp]),
+    "mj_pool_enable_log": (_i32, [_vp, _u32]),
+    "mj_log_lengths": (_i32, [_vp, _vp, _vp]),
+    "mj_log_read": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "mj_step": (_i32, [_vp, _vp, _vp, _vp]),
+    "mj_step_q": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mj_step_ev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mj_rows_count": (_i32, [_vp, _vp, _vp]),
+    "mj_rows_dev": (_vp, [_vp, _i32]),
+    "mj_encode": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "mj_encode_oracle": (_i32, [_vp, _i32, _vp, _vp]),
+    "mj_oracle_obs_rows": (_i32, [_i32]),
+    "mj_encode_timing": (_i32, [_vp, _i32, _vp, _vp]),
+    "mj_sp_timing": (_i32, [_vp, _vp, _vp]),
+    "mj_sp_phase_ticks": (_i32, [_vp, _vp, _vp]),
+    "mj_pool_set_sp_schedule": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "mj_sp_schedule_stats": (_i32, [_vp, _vp, _vp]),
+    "mj_random_policy": (_i32, [_vp, _i32, _vp, _u64, _u64, _vp, _vp]),
+    "mj_greedy_policy": (_i32, [_vp, _i32, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "mj_counters": (_i32, [_vp, _vp, _vp]),
+    "mj_results": (_i32, [_vp, _vp, _vp, _vp]),
+    "mj_pool_first_error": (_i32, [_vp, _vp, _vp]),
+    "mj_debug_table": (_i32, [_vp, _i32, _vp, _sz, _vp]),
+    "mj_debug_table_size": (_sz, []),
+    "mj_debug_layout": (_str, []),
+    "mj_obs_rows": (_i32, [_i32]),
+    "mj_algo_query": (_i32, [_vp, _i32, _vp, _vp]),
+    "mj_stat_logs": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mj_pool_stat": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mj_replay_load_pool": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "mj_grp_logs": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mj_pool_grp": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mj_augment_logs": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "mj_pool_enable_harvest": (_i32, [_vp, _u32, _u64]),
+    "mj_harvest_pending": (_i32, [_vp, _vp, _vp]),
+    "mj_harvest_take": (_i32, [_vp, _vp, _vp]),
+    "mj_harvest_destroy": (None, [_vp]),
+    "mj_harvest_info": (_i32, [_vp, _vp]),
+    "mj_harvest_games": (_i32, [_vp, _vp]),
+    "mj_harvest_read": (_i32, [_vp, _i32, _vp]),
+    "mj_harvest_stat": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mj_harvest_grp": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mj_replay_load_harvest": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+}
+SYMBOLS = list(PROTOTYPES)
 
 
 class MortalAmdError(RuntimeError):
     pass
 
 
-def _load(path=None):
-    """dlopen the C-ABI library and declare its prototypes.  `path` is for the test suite only (the host emulation of the
-    same sources, tests/host); the product always binds LIB_PATH."""
+def _hip_stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _no_stream():
+    return None
+
+
+class Library:
+    """One loaded C-ABI library: its functions, its own error text and the stream its calls take.  A pool, a harvest and
+    everything made from them call, check and take their stream through the Library they were created on, so an error is
+    never described by another library's mj_last_error (the test suite runs a host emulation next to the product)."""
+
+    def __init__(self, path, host_emulation=False):
+        self.cdll = C.CDLL(path)
+        for name, (restype, argtypes) in PROTOTYPES.items():  # plain attributes, bound once: pool.step is a hot loop
+            fn = getattr(self.cdll, name)
+            fn.restype, fn.argtypes = restype, argtypes
+            setattr(self, name, fn)
+        # stream() -> the stream argument of a call: torch's current HIP stream; the host emulation has none
+        self.stream = _no_stream if host_emulation else _hip_stream
+
+    def __getattr__(self, name):
+        """Only a name outside the header gets here (a test hook the emulation build exports): bound on first use."""
+        if not name.startswith("mj_"):
+            raise AttributeError(name)
+        fn = getattr(self.cdll, name)
+        setattr(self, name, fn)
+        return fn
+
+    def check(self, rc):
+        """rc of a call into this library -> rc, or MortalAmdError with this library's text when it reports a failure."""
+        if rc is None or rc < 0:
+            raise MortalAmdError(self.mj_last_error().decode())
+        return rc
+
+
+def _load(path=None, host_emulation=None):
+    """dlopen the C-ABI library and declare its prototypes -> Library.  `path` and `host_emulation` are for the test suite
+    only (the host emulation of the same sources, tests/host); the product always binds LIB_PATH.  A library loaded from a
+    given path is the emulation unless the caller says otherwise: an A/B build of the product comes through MORTAL_AMD_LIB."""
+    if host_emulation is None:
+        host_emulation = path is not None
     path = path or LIB_PATH
-    # torch ships its own libamdhip64; it must be in the process before libmortal_amd.so is opened, otherwise the
-    # system copy gets bound first and the two HIP runtimes disagree about the visible devices
-    import torch  # noqa: F401
-
-
     if not os.path.exists(path):
         raise MortalAmdError(
             f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). The HIP extension is mandatory; there is no CPU fallback."
         )
-    L = C.CDLL(path)
-    vp, i32, u64 = C.c_void_p, C.c_int, C.c_uint64
-    L.mj_last_error.restype = C.c_char_p
-    L.mj_tables_upload.argtypes = [vp, C.c_size_t]
-    L.mj_pool_create.restype = vp
-    L.mj_pool_create.argtypes = [i32, i32, i32, i32]
-    L.mj_pool_destroy.argtypes = [vp]
-    L.mj_pool_reset.argtypes = [vp, vp, vp, vp, vp, i32]
-    L.mj_pool_configure.argtypes = [vp, i32, i32, i32, i32]
-    L.mj_pool_set_refill.argtypes = [vp, u64]
-    L.mj_pool_set_start_stagger.argtypes = [vp, C.c_uint32, vp]
-    L.mj_step.argtypes = [vp, vp, vp, vp]
-    L.mj_step_q.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.mj_step_ev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mj_rows_count.argtypes = [vp, vp, vp]
-    L.mj_rows_dev.restype = vp
-    L.mj_rows_dev.argtypes = [vp, i32]
-    L.mj_encode.argtypes = [vp, i32, vp, vp, vp]
-    L.mj_encode_timing.argtypes = [vp, i32, vp, vp]
-    L.mj_sp_timing.argtypes = [vp, vp, vp]
-    L.mj_sp_phase_ticks.argtypes = [vp, vp, vp]
-    L.mj_pool_set_sp_schedule.argtypes = [vp, i32, i32, i32, i32, i32]
-    L.mj_sp_schedule_stats.argtypes = [vp, vp, vp]
-    L.mj_table_apply_event.argtypes = [vp, i32, vp, i32, vp]
-    L.mj_table_mark_row.argtypes = [vp, i32, i32, i32, vp]
-    L.mj_table_query.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-    L.mj_replay_load.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
-    L.mj_replay_step.argtypes = [vp, vp]
-    L.mj_replay_meta.argtypes = [vp, vp, vp]
-    L.mj_pool_enable_log.argtypes = [vp, C.c_uint32]
-    L.mj_log_lengths.argtypes = [vp, vp, vp]
-    L.mj_log_read.argtypes = [vp, i32, i32, vp, vp]
-    L.mj_encode_oracle.argtypes = [vp, i32, vp, vp]
-    L.mj_oracle_obs_rows.argtypes = [i32]
-    L.mj_random_policy.argtypes = [vp, i32, vp, u64, u64, vp, vp]
-    L.mj_greedy_policy.argtypes = [vp, i32, vp, vp, u64, u64, vp, vp]
-    L.mj_counters.argtypes = [vp, vp, vp]
-    L.mj_results.argtypes = [vp, vp, vp, vp]
-    L.mj_pool_first_error.argtypes = [vp, vp, vp]
-    L.mj_debug_table.argtypes = [vp, i32, vp, C.c_size_t, vp]
-    L.mj_debug_table_size.restype = C.c_size_t
-    L.mj_debug_layout.restype = C.c_char_p
-    L.mj_obs_rows.argtypes = [i32]
-    L.mj_algo_query.argtypes = [vp, i32, vp, vp]
-    L.mj_stat_logs.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
-    L.mj_pool_stat.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.mj_replay_load_pool.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
-    L.mj_grp_logs.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.mj_pool_grp.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.mj_augment_logs.argtypes = [vp, vp, i32, vp, vp, vp]
-    L.mj_pool_enable_harvest.argtypes = [vp, C.c_uint32, u64]
-    L.mj_harvest_pending.argtypes = [vp, vp, vp]
-    L.mj_harvest_take.argtypes = [vp, vp, vp]
-    L.mj_harvest_destroy.argtypes = [vp]
-    L.mj_harvest_destroy.restype = None
-    L.mj_harvest_info.argtypes = [vp, vp]
-    L.mj_harvest_games.argtypes = [vp, vp]
-    L.mj_harvest_read.argtypes = [vp, i32, vp]
-    L.mj_harvest_stat.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.mj_harvest_grp.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.mj_replay_load_harvest.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
-    return L
+    return Library(path, host_emulation)
 
 
 lib = _load()
-
-
-def check(rc):
-    if rc is None or (isinstance(rc, int) and rc < 0):
-        raise MortalAmdError(lib.mj_last_error().decode())
-    return rc

@@ -37,16 +37,12 @@ def set_melds(q, i, chis=(), pons=(), minkans=(), ankans=()):
 
 def run(q, lib=None):
     """Evaluate the queries on the device; returns the RESULT_DTYPE array."""
-    if lib is None:
-        from . import _lib, pool
+    from . import _lib, pool
 
+    if lib is None:
         pool._ensure_tables()
-        lib, check = _lib.lib, _lib.check
-    else:
-        def check(rc):
-            if rc < 0:
-                raise RuntimeError(lib.mj_last_error().decode())
+    L = lib or _lib.lib
     q = np.ascontiguousarray(q)
     out = np.zeros(len(q), dtype=RESULT_DTYPE)
-    check(lib.mj_algo_query(q.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p), None))
+    L.check(L.mj_algo_query(q.ctypes.data_as(C.c_void_p), len(q), out.ctypes.data_as(C.c_void_p), L.stream()))
     return out

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from .pool import ACTION_SPACE, OBS_ROWS, TablePool
-from ._lib import MortalAmdError, check
+from ._lib import MortalAmdError
 
 
 class _StackedBatch:
@@ -106,6 +106,11 @@ class _EngineRunner:
         if len(self.engines) == 1:
             self.pool.configure(1, enable_quick_eval=self.cfg[0]["quick"], version=self.cfg[0]["version"],
                                 enable_rule_based_agari_guard=self.cfg[0]["guard"])
+
+    def _seat_names(self, agent_of_seat):
+        """Per game its four seats named by the engine that plays them (game.rs:186); agent_of_seat: bit s = agent of seat s."""
+        names = [c["name"] for c in self.cfg] * (2 if len(self.cfg) == 1 else 1)  # a single engine plays both agents' seats
+        return [[names[(int(m) >> s) & 1] for s in range(4)] for m in agent_of_seat]
 
     def _policy(self, agent, obs, masks, invisible=None):
         """-> (actions int32 cuda [n], q_values f32 cuda [n,46] or None).  q-values are kept only for a guarded agent."""
@@ -215,9 +220,7 @@ class BatchRunner(_EngineRunner):
     def _log_lengths(self):
         """Event-log lengths of every table: read ONCE per cycle (the mjai-log agents of a cycle share it)."""
         if self._lens_cycle != self.cycles:
-            lens = np.zeros(self.pool.n_tables, dtype=np.uint32)
-            check(self.pool._L.mj_log_lengths(self.pool.h, lens.ctypes.data, self.pool._stream()))
-            self._lens, self._lens_cycle = lens, self.cycles
+            self._lens, self._lens_cycle = self.pool.log_lengths(), self.cycles
         return self._lens
 
     def _game_log(self, g):
@@ -226,13 +229,9 @@ class BatchRunner(_EngineRunner):
         from . import mjai_log
 
         n = int(self._log_lengths()[g])
-        if n > self.pool.log_cap:
-            raise MortalAmdError(f"event log overflow on table {g}")
         done, events = self._log_cache.get(g, (0, []))
         if n > done:
-            buf = np.empty((1, self.pool.log_cap), dtype=np.uint64)
-            check(self.pool._L.mj_log_read(self.pool.h, int(g), 1, buf.ctypes.data, self.pool._stream()))
-            events.extend(mjai_log.decode_events(buf[0, done:n]))  # in place: callers only read the list
+            events.extend(mjai_log.decode_events(self.pool.read_log(g, n)[done:]))  # in place: callers only read the list
             self._log_cache[g] = (n, events)
         return events
 
@@ -339,9 +338,7 @@ class BatchRunner(_EngineRunner):
         code, tbl = pool.first_error()
         if code:
             raise self._fail(code, tbl)
-        if pool.counters()["sp_overflow"]:
-            raise MortalAmdError("obs v4: a decision's single-player state graph exceeded the device scratch capacity "
-                                 "(SP_CAP in mortal_amd/csrc/mj_sp.hip); its SP planes would be incomplete")
+        pool.check_sp_overflow()
         scores, done = pool.results()
         if not (done == 1).all():
             raise MortalAmdError("some games did not finish")
@@ -376,11 +373,7 @@ class BatchRunner(_EngineRunner):
         augmented: the suit-swapped second pass of the reference's data loader (GameplayLoader.load_pool)."""
         if not getattr(self.pool, "log_cap", 0):
             raise MortalAmdError("gameplays: the device log is off (create the runner with keep_log or keep_stat)")
-        names_of_agent = [c["name"] for c in self.cfg]
-        if len(names_of_agent) == 1:
-            names_of_agent = names_of_agent * 2
-        names = [[names_of_agent[(int(self.agent_of_seat[g]) >> s) & 1] for s in range(4)] for g in range(self.pool.n_tables)]
-        return loader.load_pool(self.pool, seats=seats, names=names, augmented=augmented)
+        return loader.load_pool(self.pool, seats=seats, names=self._seat_names(self.agent_of_seat), augmented=augmented)
 
     @staticmethod
     def _meta(batch, row, tag, with_batch=False):
@@ -402,12 +395,9 @@ class BatchRunner(_EngineRunner):
         from . import mjai_log
 
         os.makedirs(log_dir, exist_ok=True)
-        names_of_agent = [c["name"] for c in self.cfg]
-        if len(names_of_agent) == 1:
-            names_of_agent = names_of_agent * 2
+        names = self._seat_names(self.agent_of_seat)
         paths = []
         for g, words in enumerate(self.pool.read_logs()):
-            names = [names_of_agent[(int(self.agent_of_seat[g]) >> s) & 1] for s in range(4)]  # game.rs:186
             tags = []
             events = mjai_log.decode_events(words, tags)
             for ev, tag in zip(events, tags):
@@ -422,7 +412,7 @@ class BatchRunner(_EngineRunner):
                     meta["kan_select"] = self._meta(batch, tag["kan_row"], tag)
                 ev["meta"] = meta
             name = f"{self.seeds[g][0]}_{self.seeds[g][1]}_{'abcd'[g % splits]}.json.gz"
-            paths.append(mjai_log.write_game_log_as(os.path.join(log_dir, name), names, self.seeds[g], events))
+            paths.append(mjai_log.write_game_log_as(os.path.join(log_dir, name), names[g], self.seeds[g], events))
         return paths
 
 
@@ -491,16 +481,11 @@ class SelfPlayRunner(_EngineRunner):
             for a in (0, 1):
                 if n[a]:
                     self._acts[a], self._qs[a], _ns = self._answer(a, n[a])
-        if pool.counters()["sp_overflow"]:
-            raise MortalAmdError("obs v4: a decision's single-player state graph exceeded the device scratch capacity "
-                                 "(SP_CAP in mortal_amd/csrc/mj_sp.hip); its SP planes would be incomplete")
+        pool.check_sp_overflow()
         return pool.take_harvest()
 
     def _names(self, harvest):
-        names_of_agent = [c["name"] for c in self.cfg]
-        if len(names_of_agent) == 1:
-            names_of_agent = names_of_agent * 2
-        return [[names_of_agent[(int(m) >> s) & 1] for s in range(4)] for m in harvest.games["agent_of_seat"]]
+        return self._seat_names(harvest.games["agent_of_seat"])
 
     def gameplays(self, loader, harvest, seats=None, augmented=False):
         """The training samples of every game of the harvest (GameplayLoader.load_harvest) -> a list per game of Gameplay, one per
@@ -543,8 +528,8 @@ def _rank_by_player(scores):
     return rank
 
 
-class OneVsThree:
-    """libriichi.arena.OneVsThree (arena/one_vs_three.rs:17-113)."""
+class _PyVsPy:
+    """What OneVsThree and TwoVsTwo share: the options, and playing one rank's games with a BatchRunner."""
 
     def __init__(self, *, disable_progress_bar=False, log_dir=None, deal_algo=None, collect_stat=False):
         self.disable_progress_bar = disable_progress_bar
@@ -554,6 +539,28 @@ class OneVsThree:
         # Stat.from_dir(log_dir, name) computes from the dumped files (mortal/player.py:62-71), without writing or reading them
         self.collect_stat = collect_stat
         self.stats = None
+
+    def _play(self, challenger, champion, seeds, aos, progress, splits):
+        """This rank's games -> (scores, [Stat counters of the challenger's seats, of the champion's] (zeros unless collect_stat),
+        the pool's device); the logs are dumped, `splits` files per seed, when log_dir is set.  No games: (None, zeros, None)."""
+        counters = [[0] * 44, [0] * 44]
+        if not seeds:
+            return None, counters, None
+        runner = BatchRunner([challenger, champion], seeds, aos, keep_log=self.log_dir is not None, deal_algo=self.deal_algo,
+                             keep_stat=self.collect_stat)
+        try:
+            scores = runner.run(progress=None if self.disable_progress_bar else progress)
+            if self.collect_stat:
+                counters = [t.counters() for t in runner.agent_stats()]
+            if self.log_dir is not None:
+                runner.dump_logs(self.log_dir, splits)
+        finally:
+            runner.close()
+        return scores, counters, runner.device
+
+
+class OneVsThree(_PyVsPy):
+    """libriichi.arena.OneVsThree (arena/one_vs_three.rs:17-113)."""
 
     def py_vs_py(self, challenger, champion, seed_start, seed_count):
         """Returns the rank histogram [1st, 2nd, 3rd, 4th] of the challenger over seed_count*4 hanchan."""
@@ -570,22 +577,9 @@ class OneVsThree:
         # challenger (agent 0) sits at seat g % 4, the champion (agent 1) on the other three (one_vs_three.rs:144-191)
         aos = np.array([0xF & ~(1 << (g % 4)) for g in range(g0, g1)], dtype=np.uint8)
         rankings = [0, 0, 0, 0]
-        dev = None
-        counters = [[0] * 44, [0] * 44]  # Stat counters of the challenger's / the champion's seats (collect_stat)
-        if g1 > g0:
-            runner = BatchRunner([challenger, champion], seeds, aos, keep_log=self.log_dir is not None, deal_algo=self.deal_algo,
-                                 keep_stat=self.collect_stat)
-            dev = runner.device
-            try:
-                scores = runner.run(progress=None if self.disable_progress_bar else f"rank {rank}" if world > 1 else "")
-                if self.collect_stat:
-                    counters = [t.counters() for t in runner.agent_stats()]
-                if self.log_dir is not None:
-                    runner.dump_logs(self.log_dir, 4)
-            finally:
-                runner.close()
-            for i, g in enumerate(range(g0, g1)):
-                rankings[_rank_by_player(scores[i])[g % 4]] += 1  # one_vs_three.rs:55-60
+        scores, counters, dev = self._play(challenger, champion, seeds, aos, f"rank {rank}" if world > 1 else "", 4)
+        for i, g in enumerate(range(g0, g1)):
+            rankings[_rank_by_player(scores[i])[g % 4]] += 1  # one_vs_three.rs:55-60
         if world > 1:
             red_dev = _reduce_device(backend, dev)
             rankings = sharding.allreduce_rank_histogram(rankings, device=red_dev)
@@ -603,17 +597,8 @@ class OneVsThree:
         raise NotImplementedError("akochan agents are out of scope (SURVEY.md §2 row 2)")
 
 
-class TwoVsTwo:
+class TwoVsTwo(_PyVsPy):
     """libriichi.arena.TwoVsTwo (arena/two_vs_two.rs:17-110): seed_count*2 hanchan, returns None."""
-
-    def __init__(self, *, disable_progress_bar=False, log_dir=None, deal_algo=None, collect_stat=False):
-        self.disable_progress_bar = disable_progress_bar
-        self.log_dir = log_dir
-        self.deal_algo = deal_algo  # None = pool.default_deal_algo() (rand 0.9.1 unless MORTAL_AMD_DEAL_ALGO says otherwise)
-        # our extension: py_vs_py leaves {engine name: Stat} of the whole run in self.stats, counted on the device -- what
-        # Stat.from_dir(log_dir, name) computes from the dumped files (mortal/player.py:62-71), without writing or reading them
-        self.collect_stat = collect_stat
-        self.stats = None
 
     def py_vs_py(self, challenger, champion, seed_start, seed_count):
         from . import sharding
@@ -624,20 +609,9 @@ class TwoVsTwo:
         seeds = [(int(seed_start[0]) + g // 2, int(seed_start[1])) for g in range(g0, g1)]  # two_vs_two.rs:138-140
         # split A: challenger at seats 0,2; split B: 1,3 (two_vs_two.rs:142-172)
         aos = np.array([0b1010 if g % 2 == 0 else 0b0101 for g in range(g0, g1)], dtype=np.uint8)
-        counters = [[0] * 44, [0] * 44]
-        dev = None
-        if g1 > g0:
-            runner = BatchRunner([challenger, champion], seeds, aos, keep_log=self.log_dir is not None, deal_algo=self.deal_algo,
-                                 keep_stat=self.collect_stat)
-            dev = runner.device
-            try:
-                self.last_scores = runner.run(progress=None if self.disable_progress_bar else "")
-                if self.collect_stat:
-                    counters = [t.counters() for t in runner.agent_stats()]
-                if self.log_dir is not None:
-                    runner.dump_logs(self.log_dir, 2)
-            finally:
-                runner.close()
+        scores, counters, dev = self._play(challenger, champion, seeds, aos, "", 2)
+        if scores is not None:
+            self.last_scores = scores
         if self.collect_stat:
             if world > 1:
                 flat = sharding.allreduce_counters(counters[0] + counters[1], device=_reduce_device(backend, dev))

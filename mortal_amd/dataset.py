@@ -15,7 +15,7 @@ import json
 import numpy as np
 import torch
 
-from . import mjai_log
+from . import _lib, mjai_log
 from .pool import ACTION_SPACE, OBS_ROWS, TablePool
 
 GRP_SIZE = 7
@@ -115,15 +115,21 @@ class Grp:
         return list(self.final_scores)
 
 
-def _grp_call(call, n_logs, max_kyoku):
-    """Shared by grp_logs and TablePool.log_grp: allocate the outputs, run `call(feat ptr, n_kyoku ptr, rank ptr, final ptr,
-    counts ptr)`, wrap the result -> (list of Grp or None per log, n_kyoku int32 [n], counts dict)."""
+def _grp_call(L, fn, head, n, max_kyoku, unit=None, first=0):
+    """Shared by grp_logs, TablePool.log_grp and Harvest.grp: allocate the outputs, run `fn(*head, n, max_kyoku, feat ptr,
+    n_kyoku ptr, rank ptr, final ptr, counts ptr, stream)` of library L and check it, wrap the result -> (list of Grp or None
+    per log, n_kyoku int32 [n], counts dict).  unit ("table" / "game"): a malformed log is a ValueError that names log first + i."""
+    n_logs, max_kyoku = max(int(n), 0), int(max_kyoku)  # (a negative n is the library's to refuse)
     feat = np.zeros((n_logs, max_kyoku, GRP_SIZE), dtype=np.int32)
     n_kyoku = np.zeros(n_logs, dtype=np.int32)
     rank = np.zeros((n_logs, 4), dtype=np.int32)
     final = np.zeros((n_logs, 4), dtype=np.int32)
     counts = np.zeros(3, dtype=np.int64)
-    call(feat.ctypes.data, n_kyoku.ctypes.data, rank.ctypes.data, final.ctypes.data, counts.ctypes.data)
+    L.check(fn(*head, int(n), max_kyoku, feat.ctypes.data, n_kyoku.ctypes.data, rank.ctypes.data, final.ctypes.data,
+               counts.ctypes.data, L.stream()))
+    bad = np.flatnonzero(n_kyoku < 0)
+    if unit and len(bad):
+        raise ValueError(f"{unit} {first + int(bad[0])}: malformed event log (or more than {max_kyoku} kyoku)")
     grps = []
     for i in range(n_logs):
         k = int(n_kyoku[i])
@@ -141,27 +147,9 @@ def grp_logs(words_list, max_kyoku=64, lib=None):
     mj_grp_logs).  -> (list of Grp, None for an empty or malformed log; n_kyoku int32 [n]: 0 for an empty log, -1 for a malformed
     one -- no start_kyoku, more than max_kyoku of them, an unknown event or a chain that runs past the end; counts
     dict(reduced, skipped, malformed)).  `lib` is for the test suite (the host emulation of the same sources)."""
-    import ctypes
-
-    n = len(words_list)
-    off = np.zeros(n + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(x) for x in words_list])
-    if int(off[-1]) >= 1 << 32:
-        raise ValueError("grp_logs: more than 2^32 words in one call")
-    off = off.astype(np.uint32)
-    words = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64) for x in words_list]) if n else np.zeros(0),
-                                 dtype=np.uint64)
-    stream = None
-    if lib is None:
-        from ._lib import lib
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def call(*ptrs):
-        if lib.mj_grp_logs(words.ctypes.data, off.ctypes.data, n, int(max_kyoku), *ptrs, stream) < 0:
-            from ._lib import MortalAmdError
-            raise MortalAmdError(lib.mj_last_error().decode())
-
-    return _grp_call(call, n, int(max_kyoku))
+    L = lib or _lib.lib
+    words, off, n = mjai_log.pack_logs(words_list, "grp_logs")
+    return _grp_call(L, L.mj_grp_logs, (words.ctypes.data, off.ctypes.data), n, max_kyoku)
 
 
 class Gameplay:
@@ -406,10 +394,7 @@ class GameplayLoader:
 
         Memory: all obs of the range are materialised on the device at once (137 KB per obs-v4 sample, about 600 samples per
         game and seat), so the caller bounds memory by the table range it asks for."""
-        return self._load_device("load_pool", "tables", "pool", pool.n_tables, table0, n_tables, seats, names, type(pool), pool,
-                                 pool.log_grp, lambda rp, first, tracked: rp.replay_load_pool(
-                                     pool, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle,
-                                     augmented=augmented))
+        return self._load_device(pool, table0, n_tables, seats, names, augmented)
 
     def load_harvest(self, harvest, game0=0, n_games=None, seats=None, names=None, augmented=False):
         """The samples of the games a pool in refill mode has collected (TablePool.take_harvest), with the contract of load_pool:
@@ -419,14 +404,13 @@ class GameplayLoader:
         oracle=True deals every wall from the seed recorded with the game.  augmented as in load_pool: per call, swapped on the
         device on the way into the script."""
         harvest._handle()  # (a closed Harvest is refused before anything else)
-        return self._load_device("load_harvest", "games", "harvest", harvest.n_games, game0, n_games, seats, names, harvest.pool_cls,
-                                 harvest, harvest.grp, lambda rp, first, tracked: rp.replay_load_harvest(
-                                     harvest, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle,
-                                     augmented=augmented))
+        return self._load_device(harvest, game0, n_games, seats, names, augmented)
 
-    def _load_device(self, who, unit, where, n_src, first, count, seats, names, pool_cls, src, grp_of, load_into):
-        """load_pool / load_harvest: logs [first, first + count) of a device source (`src`: device, deal_algo, log_cap) -> the
-        Gameplays.  grp_of(first, n) -> the Grps (None = skipped), load_into(replay pool, first, tracked) loads the scripts."""
+    def _load_device(self, src, first, count, seats, names, augmented):
+        """load_pool / load_harvest: logs [first, first + count) of a device source -> the Gameplays.  `src` is a TablePool or a
+        Harvest: n_logs, log_units / log_where (what the messages call it), pool_cls, device, deal_algo, log_cap, grp(first, n)
+        -> the Grps (None = skipped); the replay pool loads its scripts from it (TablePool.replay_load_<log_where>)."""
+        who, unit, where, n_src = f"load_{src.log_where}", src.log_units, src.log_where, src.n_logs
         if self.augmented:
             raise ValueError(f"{who}: a loader constructed with augmented=True is not accepted here (a pool or a harvest is read in "
                              f"both forms by one loader): construct it without and pass {who}(..., augmented=True) per call")
@@ -440,16 +424,17 @@ class GameplayLoader:
             raise ValueError(f"seats: expected {n} masks, got shape {masks.shape}")
         if names is not None and len(names) != n:
             raise ValueError(f"names: expected {n} lists of four names, got {len(names)}")
-        grps = grp_of(first, n)
+        grps = src.grp(first, n)
         games = []
         for t in range(n):
             nm = list(names[t]) if names is not None else ["", "", "", ""]
             wanted = [p for p in (self._wanted(nm) if names is not None else range(4)) if (int(masks[t]) >> p) & 1]
             games.append(dict(names=nm, wanted=wanted if grps[t] is not None else [], grp=grps[t]))
         tracked = [sum(1 << p for p in g["wanted"]) for g in games]
-        rp = pool_cls(n, version=self.version, device=str(src.device), max_rows=8 * n + 64, deal_algo=src.deal_algo)
+        rp = src.pool_cls(n, version=self.version, device=str(src.device), max_rows=8 * n + 64, deal_algo=src.deal_algo)
         try:
-            load_into(rp, first, tracked)
+            load = getattr(rp, f"replay_load_{where}")  # TablePool.replay_load_pool / replay_load_harvest
+            load(src, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle, augmented=augmented)
             # every step applies at least one event of every unfinished log, and an event takes at least one word
             samples = self._replay_samples(rp, n, src.log_cap + 8, first)
         finally:
@@ -477,8 +462,7 @@ class GameplayLoader:
         code, tbl = pool.first_error()
         if code:
             raise ValueError(f"log {table0 + tbl}: the event stream is not a legal game (error code {code})")
-        if pool.counters()["sp_overflow"]:
-            raise RuntimeError("obs v4: a sample's single-player state graph exceeded the device scratch capacity")
+        pool.check_sp_overflow(RuntimeError("obs v4: a sample's single-player state graph exceeded the device scratch capacity"))
         if obs_parts:
             obs = torch.cat(obs_parts)
             masks = torch.cat(mask_parts)

@@ -135,32 +135,34 @@ def augment_logs(logs, lib=None):
     inverse.  ValueError names the first malformed log.  `lib` is for the test suite (the host emulation of the same sources)."""
     import numpy as np
 
-    n = len(logs)
-    if n == 0:
+    from . import _lib
+
+    if len(logs) == 0:
         return []
-    off = np.zeros(n + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(x) for x in logs])
-    if int(off[-1]) >= 1 << 32:
-        raise ValueError("augment_logs: more than 2^32 words in one call")
-    off = off.astype(np.uint32)
-    words = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64) for x in logs]), dtype=np.uint64)
+    L = lib or _lib.lib
+    words, off, n = pack_logs(logs, "augment_logs")
     out = np.empty_like(words)
     counts = np.zeros(3, dtype=np.int64)
-    stream = None
-    if lib is None:
-        import ctypes
-
-        import torch
-
-        from ._lib import lib
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if lib.mj_augment_logs(words.ctypes.data, off.ctypes.data, n, out.ctypes.data, counts.ctypes.data, stream) < 0:
-        from ._lib import MortalAmdError
-        raise MortalAmdError(lib.mj_last_error().decode())
+    L.check(L.mj_augment_logs(words.ctypes.data, off.ctypes.data, n, out.ctypes.data, counts.ctypes.data, L.stream()))
     if counts[2]:
         bad = next((i for i, x in enumerate(logs) if len(x) and not _chain_ok(x)), None)
         raise ValueError(f"augment_logs: log {bad} is malformed (an unknown event type, or its event chain does not end at its end)")
     return [out[int(off[i]):int(off[i + 1])].copy() for i in range(n)]
+
+
+def pack_logs(logs, who):
+    """A list of word arrays -> (words uint64, off uint32 [n + 1], n): the logs back to back and where each starts, the form
+    mj_stat_logs, mj_grp_logs and mj_augment_logs take.  `who` names the caller in the ValueError."""
+    import numpy as np
+
+    n = len(logs)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in logs])
+    if int(off[-1]) >= 1 << 32:
+        raise ValueError(f"{who}: more than 2^32 words in one call")
+    words = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64) for x in logs]) if n else np.zeros(0),
+                                 dtype=np.uint64)
+    return words, off.astype(np.uint32), n
 
 
 def encode_events(events, augmented=False, walls=None, deal_from_seed=False):

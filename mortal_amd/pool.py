@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import tables
-from ._lib import MortalAmdError, check, lib
+from ._lib import MortalAmdError, lib
 
 OBS_ROWS = {1: 938, 2: 942, 3: 934, 4: 1012}
 ACTION_SPACE = 46
@@ -37,12 +37,8 @@ def _ensure_tables():
     global _tables_ready
     if not _tables_ready:
         p = tables.payload()
-        check(lib.mj_tables_upload(p, len(p)))
+        lib.check(lib.mj_tables_upload(p, len(p)))
         _tables_ready = True
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _load_flags(deal_from_seed, augmented):
@@ -65,19 +61,21 @@ class Harvest:
     n_games / n_words / dropped (games that found the buffer full while it was the pool's active one) / n_errors;
     games: structured array of the records (HARVEST_GAME_DTYPE), sorted by (game_id, table) -- "game i" is row i."""
 
+    log_units, log_where, _src_name = "games", "harvest", "a Harvest"  # what messages call this source (as TablePool's)
+    n_logs = property(lambda s: s.n_games)
+
     def __init__(self, pool, handle):
-        self._L = pool._L
-        self._stream = pool._stream
+        L = self._L = pool._L
         self.pool_cls = type(pool)
         self.device = pool.device
         self.deal_algo = pool.deal_algo
         self.log_cap = pool.log_cap
         self.h = handle
         info = np.zeros(4, dtype=np.int64)
-        pool._check(self._L.mj_harvest_info(self.h, info.ctypes.data))
+        L.check(L.mj_harvest_info(self.h, info.ctypes.data))
         self.n_games, self.n_words, self.dropped, self.n_errors = (int(x) for x in info)
         self.games = np.zeros(self.n_games, dtype=HARVEST_GAME_DTYPE)
-        pool._check(self._L.mj_harvest_games(self.h, self.games.ctypes.data if self.n_games else None))
+        L.check(L.mj_harvest_games(self.h, self.games.ctypes.data if self.n_games else None))
 
     def __len__(self):
         return self.n_games
@@ -94,9 +92,6 @@ class Harvest:
             raise MortalAmdError("the Harvest is closed")
         return self.h
 
-    def _fail(self):
-        return MortalAmdError(self._L.mj_last_error().decode())
-
     def read_logs(self):
         """-> list (one per game) of uint64 arrays: the event words of the game, as TablePool.read_logs returned them for its
         table before the restart (empty for a game in error)."""
@@ -104,8 +99,7 @@ class Harvest:
         out = []
         for i in range(self.n_games):
             buf = np.empty(int(self.games["n_words"][i]), dtype=np.uint64)
-            if self._L.mj_harvest_read(h, i, buf.ctypes.data if len(buf) else None) < 0:
-                raise self._fail()
+            self._L.check(self._L.mj_harvest_read(h, i, buf.ctypes.data if len(buf) else None))
             out.append(buf)
         return out
 
@@ -115,38 +109,22 @@ class Harvest:
         error is skipped."""
         from .stat import _stat_call
 
-        h = self._handle()
-
-        def call(p_seats, p_totals, p_rows, p_counts):
-            if self._L.mj_harvest_stat(h, p_seats, p_totals, p_rows, p_counts, self._stream()) < 0:
-                raise self._fail()
-
-        return _stat_call(call, self.n_games, seats, per_seat)
+        return _stat_call(self._L, self._L.mj_harvest_stat, (self._handle(),), self.n_games, seats, per_seat)
 
     def grp(self, game0=0, n=None, max_kyoku=64):
         """dataset/grp.rs `Grp` of games [game0, game0 + n) (n None = to the last), reduced on the device (mj_harvest_grp), as
         TablePool.log_grp: None for a game in error, ValueError for a malformed log."""
         from .dataset import _grp_call
 
-        h = self._handle()
-        n = self.n_games - game0 if n is None else int(n)
-
-        def call(*ptrs):
-            if self._L.mj_harvest_grp(h, int(game0), n, int(max_kyoku), *ptrs, self._stream()) < 0:
-                raise self._fail()
-
-        grps, n_kyoku, _counts = _grp_call(call, max(n, 0), max_kyoku)
-        bad = np.flatnonzero(n_kyoku < 0)
-        if len(bad):
-            raise ValueError(f"game {game0 + int(bad[0])}: malformed event log (or more than {max_kyoku} kyoku)")
-        return grps
+        n = self.n_games - game0 if n is None else n
+        return _grp_call(self._L, self._L.mj_harvest_grp, (self._handle(), int(game0)), n, max_kyoku, "game", game0)[0]
 
 
 class TablePool:
     _L = lib  # the C-ABI library (tests/host/emu_pool.py substitutes the host emulation of the same sources)
 
     def _stream(self):
-        return _stream()
+        return self._L.stream()
 
     def _bind_device(self, device):
         if not torch.cuda.is_available():
@@ -162,9 +140,7 @@ class TablePool:
         self.C = OBS_ROWS[version]
         self.max_rows = max_rows or 8 * n_tables
         self.deal_algo = default_deal_algo() if deal_algo is None else int(deal_algo)
-        self.h = self._L.mj_pool_create(n_tables, version, self.deal_algo, self.max_rows)
-        if not self.h:
-            raise MortalAmdError(self._L.mj_last_error().decode())
+        self.h = self._L.check(self._L.mj_pool_create(n_tables, version, self.deal_algo, self.max_rows))
         self.n_rows = [0, 0]
         self.n_games_total = n_tables
         self.versions = [version, version]
@@ -185,34 +161,47 @@ class TablePool:
         aos = np.ascontiguousarray(agent_of_seat if agent_of_seat is not None else np.zeros(self.n_tables),
                                    dtype=np.uint8)
         self.n_games_total = int(n_games_total or (int(gid.max()) + 1))
-        check(self._L.mj_pool_reset(self.h, nonces.ctypes.data, keys.ctypes.data, gid.ctypes.data, aos.ctypes.data,
-                                self.n_games_total))
+        self._L.check(self._L.mj_pool_reset(self.h, nonces.ctypes.data, keys.ctypes.data, gid.ctypes.data, aos.ctypes.data,
+                                            self.n_games_total))
         self.n_rows = [0, 0]
 
     def configure(self, agent, enable_quick_eval=True, enable_rule_based_agari_guard=False, version=0):
-        check(self._L.mj_pool_configure(self.h, agent, int(version), int(enable_quick_eval),
-                                    int(enable_rule_based_agari_guard)))
+        self._L.check(self._L.mj_pool_configure(self.h, agent, int(version), int(enable_quick_eval),
+                                                int(enable_rule_based_agari_guard)))
         if version:
             self.versions[agent] = version
 
     def enable_log(self, words_per_table=16384):
         """Turn the per-table mjai event log on (call before reset/step).  16384 words cover ~60 kyoku."""
-        check(self._L.mj_pool_enable_log(self.h, int(words_per_table)))
+        self._L.check(self._L.mj_pool_enable_log(self.h, int(words_per_table)))
         self.log_cap = int(words_per_table)
+
+    def log_lengths(self):
+        """-> uint32 array [n_tables]: the words each table has logged so far (more than log_cap: that log has overflowed)."""
+        lens = np.zeros(self.n_tables, dtype=np.uint32)
+        self._L.check(self._L.mj_log_lengths(self.h, lens.ctypes.data, self._L.stream()))
+        return lens
+
+    def _read_logs(self, table0, lens):
+        """The logs of tables [table0, table0 + len(lens)), cut to the lengths log_lengths gave for them."""
+        over = np.flatnonzero(lens > self.log_cap)
+        if len(over):
+            raise MortalAmdError(f"event log overflow on table {table0 + int(over[0])}")
+        buf = np.empty((len(lens), self.log_cap), dtype=np.uint64)
+        self._L.check(self._L.mj_log_read(self.h, int(table0), len(lens), buf.ctypes.data, self._L.stream()))
+        return [buf[i, :n].copy() for i, n in enumerate(lens)]
+
+    def read_log(self, table, n_words=None):
+        """-> uint64 array: the event words of one table (n_words: its length, when the caller has it from log_lengths)."""
+        n = self.log_lengths()[table] if n_words is None else n_words
+        return self._read_logs(table, np.array([n], dtype=np.uint32))[0]
 
     def read_logs(self, chunk=1024):
         """-> list (one per table) of uint64 arrays holding the event words logged so far."""
-        n = self.n_tables
-        lens = np.zeros(n, dtype=np.uint32)
-        check(self._L.mj_log_lengths(self.h, lens.ctypes.data, self._stream()))
-        if (lens > self.log_cap).any():
-            raise MortalAmdError(f"event log overflow on table {int(np.argmax(lens > self.log_cap))}")
+        lens = self.log_lengths()
         out = []
-        for t0 in range(0, n, chunk):
-            k = min(chunk, n - t0)
-            buf = np.empty((k, self.log_cap), dtype=np.uint64)
-            check(self._L.mj_log_read(self.h, t0, k, buf.ctypes.data, self._stream()))
-            out += [buf[i, :lens[t0 + i]].copy() for i in range(k)]
+        for t0 in range(0, self.n_tables, chunk):
+            out += self._read_logs(t0, lens[t0:t0 + chunk])
         return out
 
     def log_stat(self, seats=None, per_seat=False):
@@ -222,11 +211,7 @@ class TablePool:
         playing or in error are skipped."""
         from .stat import _stat_call
 
-        def call(p_seats, p_totals, p_rows, p_counts):
-            if self._L.mj_pool_stat(self.h, p_seats, p_totals, p_rows, p_counts, self._stream()) < 0:
-                raise MortalAmdError(self._L.mj_last_error().decode())
-
-        return _stat_call(call, self.n_tables, seats, per_seat)
+        return _stat_call(self._L, self._L.mj_pool_stat, (self.h,), self.n_tables, seats, per_seat)
 
     def log_grp(self, table0=0, n=None, max_kyoku=64):
         """dataset/grp.rs `Grp` of tables [table0, table0 + n) (n None = to the last), reduced from the device log in place
@@ -234,17 +219,19 @@ class TablePool:
         table whose log is malformed (or holds more than max_kyoku kyoku)."""
         from .dataset import _grp_call
 
-        n = self.n_tables - table0 if n is None else int(n)
+        n = self.n_tables - table0 if n is None else n
+        return _grp_call(self._L, self._L.mj_pool_grp, (self.h, int(table0)), n, max_kyoku, "table", table0)[0]
 
-        def call(*ptrs):
-            if self._L.mj_pool_grp(self.h, int(table0), n, int(max_kyoku), *ptrs, self._stream()) < 0:
-                raise MortalAmdError(self._L.mj_last_error().decode())
+    # ---- what a source of finished games shows GameplayLoader and replay_load_*: Harvest has the same names, over its games
+    log_units, log_where, _src_name = "tables", "pool", "a pool"
+    n_logs = property(lambda s: s.n_tables)
+    pool_cls = property(lambda s: type(s))
 
-        grps, n_kyoku, _counts = _grp_call(call, n, max_kyoku)
-        bad = np.flatnonzero(n_kyoku < 0)
-        if len(bad):
-            raise ValueError(f"table {table0 + int(bad[0])}: malformed event log (or more than {max_kyoku} kyoku)")
-        return grps
+    def grp(self, first=0, n=None, max_kyoku=64):
+        return self.log_grp(first, n, max_kyoku)
+
+    def _handle(self):
+        return self.h
 
     # ---- log replay (dataset loader)
     def replay_load(self, scripts, tracked, always_include_kan_select=True, nonces=None, keys=None):
@@ -257,9 +244,9 @@ class TablePool:
         tr = np.ascontiguousarray(tracked, dtype=np.uint8)
         n64 = np.ascontiguousarray(nonces, dtype=np.uint64) if nonces is not None else None
         k64 = np.ascontiguousarray(keys, dtype=np.uint64) if keys is not None else None
-        check(self._L.mj_replay_load(self.h, script.ctypes.data, off.ctypes.data, tr.ctypes.data, len(scripts),
-                                 int(always_include_kan_select), n64.ctypes.data if n64 is not None else None,
-                                 k64.ctypes.data if k64 is not None else None))
+        self._L.check(self._L.mj_replay_load(self.h, script.ctypes.data, off.ctypes.data, tr.ctypes.data, len(scripts),
+                                             int(always_include_kan_select), n64.ctypes.data if n64 is not None else None,
+                                             k64.ctypes.data if k64 is not None else None))
 
     def replay_load_pool(self, src, table0=0, tracked=None, always_include_kan_select=True, deal_from_seed=False, augmented=False):
         """Load the device logs of src's tables [table0, table0 + self.n_tables) as this pool's replay scripts, on the device
@@ -267,44 +254,35 @@ class TablePool:
         deal_from_seed: the walls are rebuilt from the tables' seeds, which come with the logs (the invisible obs);
         augmented: the copy swaps manzu and pinzu in every tile of the script (Event::augment; MJ_LOAD_AUGMENT), src's log stays.
         -> dict(loaded, skipped, malformed): a table still playing or in error is skipped, it replays as an empty log."""
-        tr = None
-        if tracked is not None:
-            tr = np.ascontiguousarray(tracked, dtype=np.uint8)
-            if tr.shape != (self.n_tables,):
-                raise ValueError(f"tracked: expected {self.n_tables} masks, got shape {tr.shape}")
-        if not isinstance(src, TablePool) or src._L is not self._L:
-            raise MortalAmdError("replay_load_pool: the source must be a pool of the same library")
-        counts = np.zeros(3, dtype=np.int64)
-        if self._L.mj_replay_load_pool(self.h, src.h, int(table0), tr.ctypes.data if tr is not None else None,
-                                       int(always_include_kan_select), _load_flags(deal_from_seed, augmented), counts.ctypes.data,
-                                       self._stream()) < 0:
-            raise MortalAmdError(self._L.mj_last_error().decode())
-        self.n_rows = [0, 0]
-        return dict(loaded=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2]))
+        return self._replay_load_src(TablePool, src, table0, tracked, always_include_kan_select, deal_from_seed, augmented)
 
     def replay_load_harvest(self, harvest, game0=0, tracked=None, always_include_kan_select=True, deal_from_seed=False,
                             augmented=False):
         """The same from a Harvest: games [game0, game0 + self.n_tables) of its sorted order (mj_replay_load_harvest); the seeds
         come from the records; augmented as in replay_load_pool.  -> dict(loaded, skipped, malformed): a game in error is skipped."""
+        return self._replay_load_src(Harvest, harvest, game0, tracked, always_include_kan_select, deal_from_seed, augmented)
+
+    def _replay_load_src(self, cls, src, first, tracked, always_include_kan_select, deal_from_seed, augmented):
+        """replay_load_pool / replay_load_harvest: logs [first, first + self.n_tables) of `src`, a `cls` (TablePool or Harvest)."""
         tr = None
         if tracked is not None:
             tr = np.ascontiguousarray(tracked, dtype=np.uint8)
             if tr.shape != (self.n_tables,):
                 raise ValueError(f"tracked: expected {self.n_tables} masks, got shape {tr.shape}")
-        if not isinstance(harvest, Harvest) or harvest._L is not self._L:
-            raise MortalAmdError("replay_load_harvest: the source must be a Harvest of the same library")
+        if not isinstance(src, cls) or src._L is not self._L:
+            raise MortalAmdError(f"replay_load_{cls.log_where}: the source must be {cls._src_name} of the same library")
         counts = np.zeros(3, dtype=np.int64)
-        if self._L.mj_replay_load_harvest(self.h, harvest._handle(), int(game0), tr.ctypes.data if tr is not None else None,
-                                          int(always_include_kan_select), _load_flags(deal_from_seed, augmented), counts.ctypes.data,
-                                          self._stream()) < 0:
-            raise MortalAmdError(self._L.mj_last_error().decode())
+        load = getattr(self._L, f"mj_replay_load_{cls.log_where}")
+        self._L.check(load(self.h, src._handle(), int(first), tr.ctypes.data if tr is not None else None,
+                           int(always_include_kan_select), _load_flags(deal_from_seed, augmented), counts.ctypes.data,
+                           self._L.stream()))
         self.n_rows = [0, 0]
         return dict(loaded=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2]))
 
     def replay_step(self):
-        check(self._L.mj_replay_step(self.h, self._stream()))
+        self._L.check(self._L.mj_replay_step(self.h, self._L.stream()))
         out = (C.c_int32 * 2)()
-        check(self._L.mj_rows_count(self.h, out, self._stream()))
+        self._L.check(self._L.mj_rows_count(self.h, out, self._L.stream()))
         self.n_rows = [out[0], out[1]]
         return out[0]
 
@@ -313,39 +291,34 @@ class TablePool:
         n = self.n_rows[0]
         meta = torch.empty((n, 8), dtype=torch.int32, device=self.device)
         if n:
-            check(self._L.mj_replay_meta(self.h, meta.data_ptr(), self._stream()))
+            self._L.check(self._L.mj_replay_meta(self.h, meta.data_ptr(), self._L.stream()))
         return meta
 
     def set_refill(self, nonce_stride):
-        check(self._L.mj_pool_set_refill(self.h, nonce_stride))
+        self._L.check(self._L.mj_pool_set_refill(self.h, nonce_stride))
 
     def set_start_stagger(self, cycles):
         """Steady-state runs: table t starts its first hanchan at cycle hash(t) % cycles (after reset + set_refill)."""
-        check(self._L.mj_pool_set_start_stagger(self.h, int(cycles), self._stream()))
+        self._L.check(self._L.mj_pool_set_start_stagger(self.h, int(cycles), self._L.stream()))
 
     # ---- finished games of a pool in refill mode (include/mortal_amd.h mj_pool_enable_harvest ..)
-    def _check(self, rc):
-        if rc < 0:
-            raise MortalAmdError(self._L.mj_last_error().decode())  # (the error text of the library this pool runs on)
-        return rc
-
     def enable_harvest(self, max_games, max_words):
         """Collect every finished game on the device just before its table is restarted (needs enable_log; collects while
         set_refill is on): room for max_games games and max_words log words.  A game that finds the buffer full is dropped
         and counted.  Calling it again replaces the buffer and discards what it held; max_games 0 turns harvesting off."""
-        self._check(self._L.mj_pool_enable_harvest(self.h, int(max_games), int(max_words)))
+        self._L.check(self._L.mj_pool_enable_harvest(self.h, int(max_games), int(max_words)))
 
     def harvest_pending(self):
         """-> dict(games, words, dropped) in the active buffer right now."""
         out = np.zeros(3, dtype=np.int64)
-        self._check(self._L.mj_harvest_pending(self.h, out.ctypes.data, self._stream()))
+        self._L.check(self._L.mj_harvest_pending(self.h, out.ctypes.data, self._L.stream()))
         return dict(games=int(out[0]), words=int(out[1]), dropped=int(out[2]))
 
     def take_harvest(self):
         """Detach what has been collected as a Harvest; the pool goes on collecting into a fresh buffer.  A game that has
         finished but whose table has not been restarted yet (that happens in the next step) is in the next take."""
         hp = C.c_void_p()
-        self._check(self._L.mj_harvest_take(self.h, C.byref(hp), self._stream()))
+        self._L.check(self._L.mj_harvest_take(self.h, C.byref(hp), self._L.stream()))
         return Harvest(self, hp)
 
     def step(self, actions0=None, actions1=None, q0=None, q1=None, ev0=None, ev1=None):
@@ -375,9 +348,10 @@ class TablePool:
         pq1 = q1.data_ptr() if q1 is not None and q1.numel() else None
         pe0 = ev0.data_ptr() if ev0 is not None and ev0.numel() else None
         pe1 = ev1.data_ptr() if ev1 is not None and ev1.numel() else None
-        check(self._L.mj_step_ev(self.h, p0, p1, pq0, pq1, pe0, pe1, self._stream()))
+        L = self._L
+        L.check(L.mj_step_ev(self.h, p0, p1, pq0, pq1, pe0, pe1, L.stream()))
         out = (C.c_int32 * 2)()
-        check(self._L.mj_rows_count(self.h, out, self._stream()))
+        L.check(L.mj_rows_count(self.h, out, L.stream()))
         self.n_rows = [out[0], out[1]]
         return self.n_rows
 
@@ -404,7 +378,8 @@ class TablePool:
             masks = torch.empty((n, ACTION_SPACE), dtype=torch.bool, device=self.device)
         assert obs.is_contiguous() and masks.is_contiguous() and obs.shape[0] >= n and masks.shape[0] >= n
         if n:
-            check(self._L.mj_encode(self.h, agent, obs.data_ptr(), masks.data_ptr(), self._stream()))
+            L = self._L
+            L.check(L.mj_encode(self.h, agent, obs.data_ptr(), masks.data_ptr(), L.stream()))
         return obs[:n], masks[:n]
 
     def encode_oracle(self, agent, out=None):
@@ -415,7 +390,7 @@ class TablePool:
             out = torch.empty((n, R, 34), dtype=torch.float32, device=self.device)
         assert out.device.type == self.device.type and out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= n
         assert tuple(out.shape[1:]) == (R, 34)
-        check(self._L.mj_encode_oracle(self.h, agent, out.data_ptr(), self._stream()))
+        self._L.check(self._L.mj_encode_oracle(self.h, agent, out.data_ptr(), self._L.stream()))
         return out[:n]
 
     def random_policy(self, agent, masks, seed, cycle, out=None):
@@ -423,7 +398,8 @@ class TablePool:
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device=self.device)
         if n:
-            check(self._L.mj_random_policy(self.h, agent, masks.data_ptr(), seed, cycle, out.data_ptr(), self._stream()))
+            L = self._L
+            L.check(L.mj_random_policy(self.h, agent, masks.data_ptr(), seed, cycle, out.data_ptr(), L.stream()))
         return out[:n]
 
     def greedy_policy(self, agent, masks, obs, seed, cycle, out=None):
@@ -432,59 +408,65 @@ class TablePool:
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device=self.device)
         if n:
-            check(self._L.mj_greedy_policy(self.h, agent, masks.data_ptr(), obs.data_ptr(), seed, cycle, out.data_ptr(),
-                                           self._stream()))
+            L = self._L
+            L.check(L.mj_greedy_policy(self.h, agent, masks.data_ptr(), obs.data_ptr(), seed, cycle, out.data_ptr(), L.stream()))
         return out[:n]
 
     def counters(self):
         out = (C.c_uint64 * 8)()
-        check(self._L.mj_counters(self.h, out, self._stream()))
+        self._L.check(self._L.mj_counters(self.h, out, self._L.stream()))
         return dict(steps=out[0], games=out[1], errors=out[2], decisions=out[3], quick=out[4], cycles=out[5],
                     sp_overflow=out[6])
+
+    def check_sp_overflow(self, error=None):
+        """Raise when an obs-v4 row of this pool outgrew the SP kernel's scratch; `error`: what to raise instead of the arena's."""
+        if self.counters()["sp_overflow"]:
+            raise error or MortalAmdError("obs v4: a decision's single-player state graph exceeded the device scratch capacity "
+                                          "(SP_CAP in mortal_amd/csrc/mj_sp.hip); its SP planes would be incomplete")
 
     def results(self):
         scores = np.zeros((self.n_games_total, 4), dtype=np.int32)
         done = np.zeros(self.n_games_total, dtype=np.uint8)
-        check(self._L.mj_results(self.h, scores.ctypes.data, done.ctypes.data, self._stream()))
+        self._L.check(self._L.mj_results(self.h, scores.ctypes.data, done.ctypes.data, self._L.stream()))
         return scores, done
 
     def first_error(self):
         t = C.c_int(-1)
-        code = check(self._L.mj_pool_first_error(self.h, C.byref(t), self._stream()))
+        code = self._L.check(self._L.mj_pool_first_error(self.h, C.byref(t), self._L.stream()))
         return code, t.value
 
     def encode_timing(self, enable=True):
         ms = C.c_double(0)
         n = C.c_int64(0)
-        check(self._L.mj_encode_timing(self.h, int(enable), C.byref(ms), C.byref(n)))
+        self._L.check(self._L.mj_encode_timing(self.h, int(enable), C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
     def sp_timing(self):
         """(total ms, launches) of the SP-table kernel since the last call (recorded while encode timing is on)."""
         ms = C.c_double(0)
         n = C.c_int64(0)
-        check(self._L.mj_sp_timing(self.h, C.byref(ms), C.byref(n)))
+        self._L.check(self._L.mj_sp_timing(self.h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
     def sp_phase_ticks(self):
         """Cumulative mj_k_sp phase timers (workgroup ticks, 100 MHz) and counts since the pool was created."""
         out = (C.c_uint64 * 9)()
-        check(self._L.mj_sp_phase_ticks(self.h, out, self._stream()))
+        self._L.check(self._L.mj_sp_phase_ticks(self.h, out, self._L.stream()))
         return dict(zip(("overflow", "rows", "setup", "expand", "level0", "eval", "write", "states", "dead_leaf_rows"), (int(x) for x in out)))
 
     def set_sp_schedule(self, mode=-2, max_rows=0, wide_grid=0, min_level1=0, min_level2=0):
         """Small-pool schedule of the SP kernel (include/mortal_amd.h mj_pool_set_sp_schedule): mode -1 auto / 0 never / 1 always."""
-        check(self._L.mj_pool_set_sp_schedule(self.h, mode, max_rows, wide_grid, min_level1, min_level2))
+        self._L.check(self._L.mj_pool_set_sp_schedule(self.h, mode, max_rows, wide_grid, min_level1, min_level2))
 
     def sp_schedule_stats(self):
         out = (C.c_uint64 * 4)()
-        check(self._L.mj_sp_schedule_stats(self.h, out, self._stream()))
+        self._L.check(self._L.mj_sp_schedule_stats(self.h, out, self._L.stream()))
         return dict(zip(("hybrid_launches", "rows_promoted", "rows_swept", "wide_gave_up"), (int(x) for x in out)))
 
     def debug_table(self, table):
         size = self._L.mj_debug_table_size()
         buf = (C.c_uint8 * size)()
-        check(self._L.mj_debug_table(self.h, table, buf, size, self._stream()))
+        self._L.check(self._L.mj_debug_table(self.h, table, buf, size, self._L.stream()))
         raw = bytes(buf)
         out = {}
         for ent in self._L.mj_debug_layout().decode().strip(";").split(";"):

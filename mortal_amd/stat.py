@@ -302,9 +302,9 @@ class Stat:
         return "Stat { " + ", ".join(f"{f}: {getattr(self, f)}" for f in _FIELDS) + " }"
 
 
-def _stat_call(call, n_logs, seats, per_seat):
-    """Shared by stat_logs and TablePool.log_stat: allocate the outputs, run `call(seats ptr, totals ptr, per-seat ptr, counts
-    ptr)`, wrap the result."""
+def _stat_call(L, fn, head, n_logs, seats, per_seat, groups=()):
+    """Shared by stat_logs, TablePool.log_stat and Harvest.stat: allocate the outputs, run `fn(*head, seats ptr, *groups, totals
+    ptr, per-seat ptr, counts ptr, stream)` of library L and check it, wrap the result."""
     import numpy as np
 
     if seats is not None:
@@ -314,8 +314,8 @@ def _stat_call(call, n_logs, seats, per_seat):
     totals = np.zeros((2, len(_FIELDS)), dtype=np.int64)
     rows = np.zeros((n_logs, 4, len(_FIELDS)), dtype=np.int64) if per_seat else None
     counts = np.zeros(3, dtype=np.int64)
-    call(seats.ctypes.data if seats is not None else None, totals.ctypes.data, rows.ctypes.data if per_seat else None,
-         counts.ctypes.data)
+    L.check(fn(*head, seats.ctypes.data if seats is not None else None, *groups, totals.ctypes.data,
+               rows.ctypes.data if per_seat else None, counts.ctypes.data, L.stream()))
     return ([Stat.from_counters(totals[0]), Stat.from_counters(totals[1])], rows,
             dict(reduced=int(counts[0]), skipped=int(counts[1]), malformed=int(counts[2])))
 
@@ -328,34 +328,16 @@ def stat_logs(words_list, seats=None, groups=None, per_seat=False, lib=None):
     array [n, 4, 44] in STAT_FIELDS order or None, counts dict(reduced, skipped, malformed)): an empty log is skipped, a
     malformed one (its event chain runs past its end, or an unknown event type) is counted and contributes nothing.
     `lib` is for the test suite (the host emulation of the same sources)."""
-    import ctypes
-
     import numpy as np
 
-    n = len(words_list)
-    off = np.zeros(n + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(x) for x in words_list])
-    if int(off[-1]) >= 1 << 32:
-        raise ValueError("stat_logs: more than 2^32 words in one call")
-    off = off.astype(np.uint32)
-    words = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64) for x in words_list]) if n else np.zeros(0),
-                                 dtype=np.uint64)
+    from . import _lib
+    from .mjai_log import pack_logs
+
+    L = lib or _lib.lib
+    words, off, n = pack_logs(words_list, "stat_logs")
     if groups is not None:
         groups = np.ascontiguousarray(groups, dtype=np.uint8)
         if groups.shape != (n,):
             raise ValueError(f"groups: expected {n} bytes, got shape {groups.shape}")
-    stream = None
-    if lib is None:
-        import torch
-
-        from ._lib import lib
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def call(p_seats, p_totals, p_rows, p_counts):
-        rc = lib.mj_stat_logs(words.ctypes.data, off.ctypes.data, n, p_seats, groups.ctypes.data if groups is not None else None,
-                              p_totals, p_rows, p_counts, stream)
-        if rc < 0:
-            from ._lib import MortalAmdError
-            raise MortalAmdError(lib.mj_last_error().decode())
-
-    return _stat_call(call, n, seats, per_seat)
+    return _stat_call(L, L.mj_stat_logs, (words.ctypes.data, off.ctypes.data, n), n, seats, per_seat,
+                      groups=(groups.ctypes.data if groups is not None else None,))

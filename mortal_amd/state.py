@@ -12,8 +12,8 @@ import json
 import numpy as np
 
 from . import mjai_log
-from ._lib import MortalAmdError, check, lib
-from .pool import TablePool, _stream
+from ._lib import MortalAmdError
+from .pool import TablePool
 
 _CAN_BITS = ["can_discard", "can_chi_low", "can_chi_mid", "can_chi_high", "can_pon", "can_daiminkan", "can_kakan",
              "can_ankan", "can_riichi", "can_tsumo_agari", "can_ron_agari", "can_ryukyoku"]
@@ -84,8 +84,8 @@ class PlayerState:
         if ev["type"] in ("start_game", "end_game"):
             ev = {"type": "end_kyoku"}  # same effect on a PlayerState: only the per-event reset of last_cans
         words = mjai_log.encode_events([ev])
-        self._need_pool()
-        check(self._pool._L.mj_table_apply_event(self._pool.h, 0, words.ctypes.data, len(words), self._pool._stream()))
+        L = self._need_pool()
+        L.check(L.mj_table_apply_event(self._pool.h, 0, words.ctypes.data, len(words), L.stream()))
         self._cache = None
         code, _ = self._pool.first_error()
         if code:
@@ -180,8 +180,10 @@ class PlayerState:
         return None
 
     def _need_pool(self):
+        """-> the library this state's pool runs on."""
         if self._pool is None:
             raise MortalAmdError("this PlayerState is a read-only copy of an arena table (PlayerState.view)")
+        return self._pool._L
 
     def _table(self):
         if self._cache is None:
@@ -190,23 +192,23 @@ class PlayerState:
         return self._cache
 
     def _query(self, what, args=()):
-        self._need_pool()
+        L = self._need_pool()
         a = np.zeros(8, dtype=np.int32)
         a[:len(args)] = args
         out = np.zeros(8, dtype=np.int32)
-        check(self._pool._L.mj_table_query(self._pool.h, 0, self.player_id, what, a.ctypes.data, out.ctypes.data, self._pool._stream()))
+        L.check(L.mj_table_query(self._pool.h, 0, self.player_id, what, a.ctypes.data, out.ctypes.data, L.stream()))
         self._cache = None
         return out
 
     # ---- obs (state/obs_repr.rs:776-791)
     def encode_obs(self, version, at_kan_select):
-        self._need_pool()
+        L = self._need_pool()
         self._pool.configure(0, version=int(version))
-        check(self._pool._L.mj_table_mark_row(self._pool.h, 0, self.player_id, int(bool(at_kan_select)), self._pool._stream()))
+        L.check(L.mj_table_mark_row(self._pool.h, 0, self.player_id, int(bool(at_kan_select)), L.stream()))
         import ctypes as C
 
         out = (C.c_int32 * 2)()
-        check(self._pool._L.mj_rows_count(self._pool.h, out, self._pool._stream()))
+        L.check(L.mj_rows_count(self._pool.h, out, L.stream()))
         self._pool.n_rows = [out[0], out[1]]
         obs, masks = self._pool.encode(0)
         return obs[0].cpu().numpy(), masks[0].cpu().numpy()

@@ -22,10 +22,9 @@ def emu_lib():
 
         from mortal_amd import _lib, tables
 
-        _emu = _lib._load(build_emu.build())
+        _emu = _lib._load(build_emu.build(), host_emulation=True)  # (its calls take no stream)
         p = tables.payload()
-        if _emu.mj_tables_upload(p, len(p)) != 0:
-            raise RuntimeError(_emu.mj_last_error().decode())
+        _emu.check(_emu.mj_tables_upload(p, len(p)))
     return _emu
 
 
@@ -34,9 +33,6 @@ def make_pool_class():
 
     class EmuPool(TablePool):
         _L = emu_lib()
-
-        def _stream(self):
-            return None
 
         def _bind_device(self, device):
             self.device = torch.device("cpu")

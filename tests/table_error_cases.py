@@ -25,6 +25,7 @@ import json
 import os
 
 import numpy as np
+import pytest
 import torch
 
 import parity_util
@@ -358,8 +359,7 @@ def check_row_capacity(oracle, pool_cls, n_clean=64):
             pool.step()
         except MortalAmdError as e:
             raised = e
-        # (the text is read from the pool's own library: the emulated one keeps its own last-error string)
-        assert raised is not None and "row capacity exceeded" in pool._L.mj_last_error().decode()
+        assert raised is not None and "row capacity exceeded" in str(raised)
         obs = torch.zeros((8, pool.C, 34), dtype=torch.float32, device=pool.device)
         masks = torch.zeros((8, 46), dtype=torch.bool, device=pool.device)
         assert pool._L.mj_encode(pool.h, 0, obs.data_ptr(), masks.data_ptr(), pool._stream()) < 0
@@ -381,7 +381,7 @@ def check_row_capacity(oracle, pool_cls, n_clean=64):
                 pass
         except MortalAmdError as e:
             raised = e
-        assert raised is not None and "row capacity exceeded" in pool._L.mj_last_error().decode()
+        assert raised is not None and "row capacity exceeded" in str(raised)
         meta = torch.zeros((1, 8), dtype=torch.int32, device=pool.device)
         assert pool._L.mj_replay_meta(pool.h, meta.data_ptr(), pool._stream()) < 0
         assert "mj_rows_count" in pool._L.mj_last_error().decode() and not meta.any()
@@ -389,6 +389,35 @@ def check_row_capacity(oracle, pool_cls, n_clean=64):
         pool.close()
     st = parity_util.run_lockstep(oracle, n_clean, version=3, max_cycles=50, obs_every=10, pool_cls=pool_cls, deal_algo=0, verbose=False)
     assert st["cycles"] == 50 and st["obs_checked"] > 0
+
+
+def check_error_texts(pool_cls):
+    """A call the C side refuses raises MortalAmdError with the text of the library the pool runs on (the host emulation keeps
+    its own last-error string, apart from the product library's): a pool of 4 tables, log off, no refill."""
+    from mortal_amd.state import PlayerState
+
+    def refused(call):
+        with pytest.raises(MortalAmdError) as ex:
+            call()
+        return str(ex.value)
+
+    pool = pool_cls(4, version=3, deal_algo=0)
+    try:
+        assert refused(lambda: pool.configure(5)) == "bad agent"
+        assert refused(pool.read_logs) == "event log is not enabled"
+        assert refused(pool.log_lengths) == "event log is not enabled"
+        assert "needs the refill mode" in refused(lambda: pool.set_start_stagger(3))
+        assert "mj_pool_stat: the event log is not enabled" in refused(pool.log_stat)
+        # state.py's own calls go through the pool's library too.  A view answers from its copy and has no pool to call, so this
+        # one is handed the pool it was taken from, and a seat that mj_table_query's argument check refuses
+        st = PlayerState.view(pool, 0, 0)
+        st._pool, st.player_id = pool, 4
+        try:
+            assert refused(st.real_time_shanten) == "bad table / seat"
+        finally:
+            st._pool = None
+    finally:
+        pool.close()
 
 
 REFILL_VICTIMS = ((5, 10, "ryukyoku_none"), (20, 14, "id_46"), (63, 14, "discard_not_in_hand"))  # (table, first cycle, kind)

@@ -55,6 +55,26 @@ def test_emu_row_capacity(oracle, emu):
     T.check_row_capacity(oracle, emu)
 
 
+def test_emu_error_texts_are_the_pools_own_librarys(emu):
+    T.check_error_texts(emu)
+
+
+def test_emu_error_text_does_not_cross_libraries(emu):
+    """The emulation and the product library each keep their last-error string: a refused call on an EmuPool raises the
+    emulation's text and leaves the product library's as it was."""
+    from mortal_amd import _lib
+
+    pool = emu(4, version=3, deal_algo=0)
+    try:
+        before = _lib.lib.mj_last_error()
+        with pytest.raises(_lib.MortalAmdError) as ex:
+            pool.configure(5)
+        assert pool._L is not _lib.lib and _lib.lib.mj_last_error() == before != b"bad agent"
+        assert pool._L.mj_last_error().decode() == str(ex.value) == "bad agent"
+    finally:
+        pool.close()
+
+
 def test_emu_refill_restarts_a_dead_table_clean(oracle, emu):
     """Six tables, three of them dying of 44, of 46 and of a discard of a tile not held (the GPU leg has them on lanes 5, 20 and 63)."""
     st = T.check_refill_restart(oracle, emu, n=6, max_cycles=6000,

@@ -44,6 +44,10 @@ def test_gpu_row_capacity(oracle):
     T.check_row_capacity(oracle, TablePool)
 
 
+def test_gpu_error_texts_are_the_pools_own_librarys():
+    T.check_error_texts(TablePool)
+
+
 def test_gpu_refill_restarts_a_dead_table_clean(oracle):
     st = T.check_refill_restart(oracle, TablePool, n=64)
     assert st["fired"] == 3 and st["side_rows"] > 1000

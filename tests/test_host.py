@@ -19,6 +19,15 @@ def test_abi_exports_every_declared_symbol():
     from mortal_amd import _lib
 
     assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
+    # every declaration's parameter list (plain C, over several lines for some, `(void)` for none) has as many entries as the
+    # binding's argtypes
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S)
+    params = {name: [p for p in re.split(r"\s*,\s*", plist.strip()) if p != "void"]
+              for name, plist in re.findall(r"\b(mj_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code)}
+    assert set(params) == declared, set(params) ^ declared
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        assert len(argtypes) == len(params[name]) and "" not in params[name], (name, params[name], argtypes)
+    assert len(params["mj_pool_set_sp_schedule"]) == 6 and params["mj_last_error"] == []
     L = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(L, name), name

@@ -228,9 +228,7 @@ def main():
     sizes = []
     for n in args.tables:
         pool, cycles, play_s = play(n, args.log_words)
-        lens = np.zeros(n, dtype=np.uint32)
-        from mortal_amd._lib import check
-        check(pool._L.mj_log_lengths(pool.h, lens.ctypes.data, pool._stream()))
+        lens = pool.log_lengths()
         seeds = [(10000 + t, KEY) for t in range(n)]
         runs = []
         for r in range(args.repeats):

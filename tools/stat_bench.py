@@ -72,10 +72,7 @@ def main():
     dev_s = statistics.median(times)
     assert counts == dict(reduced=n, skipped=0, malformed=0), counts
 
-    lens = np.zeros(n, dtype=np.uint32)
-    from mortal_amd._lib import check
-    check(pool._L.mj_log_lengths(pool.h, lens.ctypes.data, pool._stream()))
-    words = int(lens.sum())
+    words = int(pool.log_lengths().sum())
 
     host_s = None
     if not args.skip_host:
