@@ -34,6 +34,9 @@
  *                         arena/result.rs:19-51 (what a GameResult keeps: seed, scores, log)
  *   mj_harvest_stat       stat.rs:263-441 + 443-498, as mj_pool_stat      mj_harvest_grp   dataset/grp.rs:90-164, as mj_pool_grp
  *   mj_replay_load_harvest   arena/result.rs:32-51 -> dataset/gameplay.rs:66-124, as mj_replay_load_pool
+ *   mj_samples_create / _destroy / _append / _truncate / _info / _meta   mortal/dataloader.py:45-113 (the buffer populate_buffer fills
+ *                         and shuffles) over dataset/gameplay.rs:239-443 entries, kept as records
+ *   mj_samples_encode, mj_samples_encode_oracle   state/obs_repr.rs:126-630, dataset/invisible.rs: the obs of buffered entries, on demand
  */
 #ifndef MORTAL_AMD_H
 #define MORTAL_AMD_H
@@ -313,6 +316,39 @@ int mj_harvest_grp(const MjHarvest* h, int game0, int n, int max_kyoku, int32_t*
  * and the harvest as they were. */
 int mj_replay_load_harvest(MjPool* dst, const MjHarvest* h, int game0, const uint8_t* tracked_host /* NULL ok */,
                            int always_include_kan_select, int flags /* MJ_LOAD_* */, int64_t counts_out[3], void* stream);
+
+/* ---- Sample store: the replay buffer of mortal/dataloader.py:45-113 (populate_buffer keeps every obs of a batch of files and
+ * shuffles them), kept as records (kernels: mortal_amd/csrc/mj_samples.hip).  The encoders read nothing of a decision but its
+ * snapshot record and its row descriptor, so a store keeps those -- about 2 KB per sample where an obs takes 127 to 138 KB -- with the
+ * eight int32 of mj_replay_meta, and encodes any list of its samples on demand with the kernels of mj_encode / mj_encode_oracle,
+ * bit for bit what they gave when the decision was replayed.  Samples are appended from replay pools (mj_replay_load*) and
+ * addressed by index, in the order they were appended.
+ * capacity: 1 .. 2^28 - 1 samples (an index takes the table bits of a row descriptor); version: obs version 1..4; batch_rows: rows
+ * per encode launch (a larger request is served in chunks; for obs v4 it sizes the SP work areas like a pool of that many tables).
+ * NULL + mj_last_error on failure.  A store lives on the device of the lookup tables, like a pool. */
+typedef struct MjSamples MjSamples;
+MjSamples* mj_samples_create(int64_t capacity, int version, int batch_rows);
+void mj_samples_destroy(MjSamples* s);
+/* dataset/gameplay.rs:239-443 (one entry per decision of a tracked seat): the rows of agent 0 of replay_pool's last mj_replay_step
+ * (mj_rows_count done) become samples count .. count + rows - 1, all of them or none: each row its own copy of its table's record, even
+ * where several rows of the step name one table.  meta [1] of a sample is log_base + its table.  Ordered behind the pool's
+ * snapshot, whatever its stream.  An error if the pool has no replay script (the label comes from it) or the rows do not fit. */
+int mj_samples_append(MjSamples* s, MjPool* replay_pool, int32_t log_base, void* stream);
+/* Forget the samples from `count` on (count <= the current count; 0 = clear). */
+int mj_samples_truncate(MjSamples* s, int64_t count);
+/* out = {count, capacity, device bytes per sample, overflow flags: the encoder's op list | SP hash-set overflows of every encode so
+ * far (must stay 0, as mj_counters [6])}; waits for the stream of the last encode. */
+int mj_samples_info(const MjSamples* s, int64_t out4[4]);
+/* The int32[8] of samples [first, first + n) to host memory: {label, game, seat, kyoku index, turn, shanten, is kan-select row,
+ * event index} (mj_replay_meta's, game = log_base + table).  Synchronous. */
+int mj_samples_meta(const MjSamples* s, int64_t first, int64_t n, int32_t* meta_host /* [n][8] */, void* stream);
+/* agent/mortal.rs:252-287 -> state/obs_repr.rs:126-630 over stored decisions: obs_dev [n][C][34] f32, masks_dev [n][46] u8 of the
+ * samples idx_host[0..n) names (a host array; any order, duplicates allowed), as mj_encode wrote them for those rows.  Every index is
+ * checked before anything is queued: a refused call writes nothing.  Asynchronous on `stream`; idx_host may go when the call returns. */
+int mj_samples_encode(MjSamples* s, const int32_t* idx_host, int n, float* obs_dev, uint8_t* masks_dev, void* stream);
+/* dataset/invisible.rs (Invisible::encode) over stored decisions: out_dev [n][mj_oracle_obs_rows][34] f32, every undrawn yama tile
+ * listed as mj_encode_oracle does for a replay pool.  Meaningful for samples whose pool was loaded with its walls (MJ_LOAD_DEAL_FROM_SEED). */
+int mj_samples_encode_oracle(MjSamples* s, const int32_t* idx_host, int n, float* out_dev, void* stream);
 
 /* First table in error: returns its error code (>0) and index, or 0. */
 int mj_pool_first_error(MjPool* pool, int* table_out, void* stream);

@@ -12,7 +12,7 @@ import torch
 _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MORTAL_AMD_LIB") or os.path.join(_DIR, "libmortal_amd.so")  # env override: A/B builds
 
-_vp, _i32, _u32, _u64, _sz, _str = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_char_p
+_vp, _i32, _u32, _u64, _i64, _sz, _str = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_int64, C.c_size_t, C.c_char_p
 # name: (restype, argtypes) of every symbol include/mortal_amd.h declares (tests/test_host.py checks the names and the number
 # of parameters against the header, and that the library exports all of them)
 PROTOTYPES = {
@@ -73,6 +73,14 @@ PROTOTYPES = {
     "mj_harvest_stat": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mj_harvest_grp": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mj_replay_load_harvest": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "mj_samples_create": (_vp, [_i64, _i32, _i32]),
+    "mj_samples_destroy": (None, [_vp]),
+    "mj_samples_append": (_i32, [_vp, _vp, _i32, _vp]),
+    "mj_samples_truncate": (_i32, [_vp, _i64]),
+    "mj_samples_info": (_i32, [_vp, _vp]),
+    "mj_samples_meta": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "mj_samples_encode": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "mj_samples_encode_oracle": (_i32, [_vp, _vp, _i32, _vp, _vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 
@@ -102,6 +110,7 @@ class Library:
             setattr(self, name, fn)
         # stream() -> the stream argument of a call: torch's current HIP stream; the host emulation has none
         self.stream = _no_stream if host_emulation else _hip_stream
+        self.host_emulation = bool(host_emulation)  # its "device" memory is host memory (SampleStore puts its tensors there)
 
     def __getattr__(self, name):
         """Only a name outside the header gets here (a test hook the emulation build exports): bound on first use."""

@@ -375,6 +375,15 @@ class BatchRunner(_EngineRunner):
             raise MortalAmdError("gameplays: the device log is off (create the runner with keep_log or keep_stat)")
         return loader.load_pool(self.pool, seats=seats, names=self._seat_names(self.agent_of_seat), augmented=augmented)
 
+    def sample_store(self, loader, seats=None, augmented=False, store=None, capacity=None, batch_rows=1024):
+        """After run(): the same samples into a SampleStore (GameplayLoader.store_pool) -- every decision kept as its 2 KB record
+        and encoded when a batch draws it, instead of every obs at once.  store: append to this one (successive runs fill one
+        buffer); else a new one of `capacity` samples.  -> the store."""
+        if not getattr(self.pool, "log_cap", 0):
+            raise MortalAmdError("sample_store: the device log is off (create the runner with keep_log or keep_stat)")
+        return loader.store_pool(self.pool, seats=seats, names=self._seat_names(self.agent_of_seat), augmented=augmented,
+                                 store=store, capacity=capacity, batch_rows=batch_rows)
+
     @staticmethod
     def _meta(batch, row, tag, with_batch=False):
         """Metadata of one decision (agent/mortal.rs:161-186 gen_meta + :575-591), keys in the order of mjai::Metadata."""
@@ -492,6 +501,12 @@ class SelfPlayRunner(_EngineRunner):
         wanted seat, the seats named by engine as BatchRunner.gameplays names them.  seats: 4-bit seat mask per game; augmented:
         the suit-swapped form of the same games."""
         return loader.load_harvest(harvest, seats=seats, names=self._names(harvest), augmented=augmented)
+
+    def sample_store(self, loader, harvest, seats=None, augmented=False, store=None, capacity=None, batch_rows=1024):
+        """The games of the harvest into a SampleStore (GameplayLoader.store_harvest), named as gameplays names them.  store:
+        append to this one -- the replay buffer that successive harvests fill; else a new one of `capacity` samples."""
+        return loader.store_harvest(harvest, seats=seats, names=self._names(harvest), augmented=augmented, store=store,
+                                    capacity=capacity, batch_rows=batch_rows)
 
     def stats(self, harvest):
         """{engine name: Stat} over the games of the harvest (games in error are left out)."""

@@ -1,5 +1,5 @@
 // C-ABI host side (include/mortal_amd.h): pool life-cycle and kernel launches.  One translation unit for the whole
-// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip / mj_gameplay.hip / mj_harvest.hip
+// library; the kernels live in mj_step.hip / mj_replay.hip / mj_encode.hip / mj_sp.hip / mj_stat.hip / mj_gameplay.hip / mj_harvest.hip / mj_samples.hip
 // (mj_log.h: what the kernels over packed logs share).
 // Host float math below builds bit-exact LUTs: compile with -ffp-contract=off.
 // Ownership: whatever the host takes from the HIP runtime is held by an owner of mj_host.h and released by its destructor; a call that
@@ -25,6 +25,7 @@
 #include "mj_stat.hip"
 #include "mj_gameplay.hip"
 #include "mj_harvest.hip"
+#include "mj_samples.hip"
 
 static_assert(sizeof(MjAlgoQuery) == 72, "MjAlgoQuery layout");
 // include/mortal_amd.h mj_algo_query: one thread per query, the same device functions the step / encode / SP kernels call
@@ -737,10 +738,18 @@ int mj_rows_count(MjPool* P, int32_t out[2], void* stream) {
 }
 const uint32_t* mj_rows_dev(MjPool* P, int agent) { return P ? P->rows[agent & 1].get() : nullptr; }
 
-static SpParams sp_params(const MjPool* P, const SpResources& R, int agent, float* obs, int n) {
+// What an encode launch reads: the records and the descriptors that index them.  mj_encode / mj_encode_oracle pass the pool's own
+// snapshot and row list, a sample store its record array and the descriptors of the requested samples (mj_samples_encode).
+struct EncSrc {
+    const TableOne* snap;
+    const uint32_t* rows;
+};
+static EncSrc pool_src(const MjPool* P, int agent) { return {P->snap.get(), P->rows[agent & 1].get()}; }
+
+static SpParams sp_params(const EncSrc& src, const SpResources& R, float* obs, int n) {
     SpParams kp{};
-    kp.snap = P->snap.get();
-    kp.rows = P->rows[agent & 1].get();
+    kp.snap = src.snap;
+    kp.rows = src.rows;
     kp.n_rows = n;
     kp.tables = g_tables.dev;
     kp.obs = obs;
@@ -753,7 +762,7 @@ static SpParams sp_params(const MjPool* P, const SpResources& R, int agent, floa
 
 // The SP kernels' resources, sized at the pool's first obs-v4 encode (mj_pool_set_sp_schedule may change the mode until then).
 // All or nothing: they are built in a local and moved into the pool last, so after a failure the next v4 encode tries again.
-static int sp_setup(MjPool* P, int agent, float* obs, hipStream_t s) {
+static int sp_setup(MjPool* P, const EncSrc& src, float* obs, hipStream_t s) {
     SpResources R;
     const PoolKnobs& K = P->knobs;
     if (R.err.alloc(SP_ERR_WORDS)) return -1;
@@ -785,7 +794,7 @@ static int sp_setup(MjPool* P, int agent, float* obs, hipStream_t s) {
         // HSA_STATUS_ERROR_OUT_OF_RESOURCES in the middle of a run -- at pool set-up it is an ordinary, early failure.
         HIP_OK(hipMemsetAsync(R.queue.get(), 0, SP_Q_WORDS * sizeof(int), s));
         HIP_OK(hipStreamSynchronize(s));
-        SpParams w = sp_params(P, R, agent, obs, 0);
+        SpParams w = sp_params(src, R, obs, 0);
         w.sweep = 1;
         hipLaunchKernelGGL(mj_k_sp_wide, dim3(1), dim3(SP_WIDE_THREADS), 0, s, w);
         hipLaunchKernelGGL(mj_k_sp_promo, dim3(1), dim3(SP_THREADS), 0, R.stream2.get(), w);
@@ -838,10 +847,10 @@ static int rowdump_end(MjPool* P, const SpParams& kp, DevBuf<uint32_t>& dump, hi
 #endif
 
 // One SP launch over the n rows just encoded: the row order, then mj_k_sp alone or the small-pool schedule
-static int sp_launch(MjPool* P, int agent, float* obs, int n, hipStream_t s) {
+static int sp_launch(MjPool* P, const EncSrc& src, float* obs, int n, hipStream_t s) {
     SpResources& R = P->sp;
     HIP_OK(hipMemsetAsync(R.queue.get(), 0, SP_Q_WORDS * sizeof(int), s));
-    SpParams kp = sp_params(P, R, agent, obs, n);
+    SpParams kp = sp_params(src, R, obs, n);
     kp.prof = P->knobs.sp_prof ? R.err.get() : nullptr;
 #ifdef SP_ROWDUMP
     DevBuf<uint32_t> dump;
@@ -868,7 +877,7 @@ static int sp_launch(MjPool* P, int agent, float* obs, int n, hipStream_t s) {
     kp.promo_min[2] = P->sp_promo_min[2] > 0 ? P->sp_promo_min[2] : n <= 12000 ? 400 : 1 << 30;
     kp.n_narrow = grid;
     // queue order: rows counting-sorted by cost class, heaviest first (inside the timed mj_k_sp region)
-    hipLaunchKernelGGL(mj_k_order_classify, dim3((n + 255) / 256), dim3(256), 0, s, P->snap.get(), kp.rows, n, R.cls.get(), R.queue.get() + 1);
+    hipLaunchKernelGGL(mj_k_order_classify, dim3((n + 255) / 256), dim3(256), 0, s, src.snap, kp.rows, n, R.cls.get(), R.queue.get() + 1);
     hipLaunchKernelGGL(mj_k_order_scatter, dim3((n + 255) / 256), dim3(256), 0, s, R.cls.get(), n, R.queue.get() + 1, R.queue.get() + 9,
                        R.order.get());
     if (!hybrid) {
@@ -905,33 +914,29 @@ static int sp_launch(MjPool* P, int agent, float* obs, int n, hipStream_t s) {
     return 0;
 }
 
-int mj_encode(MjPool* P, int agent, float* obs, uint8_t* masks, void* stream) {
-    if (!P) return fail("null pool");
-    if (!P->rows_valid) return fail("mj_rows_count must be called after mj_step and before mj_encode");
-    int n = P->last_rows[agent & 1];
-    if (n == 0) return 0;
+// The launches of one encode over rows [0, n) of `src`: the encoder of C's obs version for `agent`, then for obs v4 the SP block.  C owns
+// what they need beside the records: version, the op-list flag, the SP resources (set up at the first v4 call), knobs and timers.
+static int encode_launch(MjPool* C, int agent, const EncSrc& src, int n, float* obs, uint8_t* masks, hipStream_t s) {
     EncParams ep;
-    ep.blocks = P->blocks.get();
-    ep.rows = P->rows[agent & 1].get();
+    ep.blocks = C->blocks.get();
+    ep.rows = src.rows;
     ep.n_rows = n;
     ep.tables = g_tables.dev;
     ep.obs = obs;
     ep.masks = masks;
-    ep.version = P->version[agent & 1];
+    ep.version = C->version[agent & 1];
     ep.C = mj_obs_rows(ep.version);
-    ep.snap = P->snap.get();
+    ep.snap = src.snap;
     ep.decay_lut = g_tables.decay;
     ep.rbf_score = g_tables.rbf_score;
     ep.rbf_6 = g_tables.rbf_6;
     ep.rbf_12 = g_tables.rbf_12;
     ep.rbf_23 = g_tables.rbf_23;
-    ep.err_flag = P->enc_flag.get();
-    size_t lds = enc_lds_bytes(ep.version, P->knobs.enc_lds_pad);
-    hipStream_t s = (hipStream_t)stream;
-    if (wait_snapshot(P, s)) return -1;
-    if (P->timing && P->enc_timer.begin(s)) return -1;
+    ep.err_flag = C->enc_flag.get();
+    size_t lds = enc_lds_bytes(ep.version, C->knobs.enc_lds_pad);
+    if (C->timing && C->enc_timer.begin(s)) return -1;
 #if ENC_PERSIST
-    const int egrid = std::min(n, P->knobs.enc_grid);
+    const int egrid = std::min(n, C->knobs.enc_grid);
 #else
     const int egrid = n;
 #endif
@@ -941,17 +946,27 @@ int mj_encode(MjPool* P, int agent, float* obs, uint8_t* masks, void* stream) {
         case 3: hipLaunchKernelGGL(mj_k_encode<3>, dim3(egrid), dim3(ENC_THREADS), lds, s, ep); break;
         default: hipLaunchKernelGGL(mj_k_encode<4>, dim3(egrid), dim3(ENC_THREADS), lds, s, ep); break;
     }
-    if (P->timing && P->enc_timer.end(s)) return -1;
+    if (C->timing && C->enc_timer.end(s)) return -1;
     HIP_OK(hipGetLastError());
     if (ep.version != 4) return 0;
     // SP block, rows 889..1011: one decision row per persistent workgroup (mj_sp.hip: mj_k_sp; the per-phase pipeline of round 4 that
     // lost to it: DESIGN.md section 6)
-    if (!P->sp.work && sp_setup(P, agent, obs, s)) return -1;
-    if (P->timing && P->sp_timer.begin(s)) return -1;
-    if (sp_launch(P, agent, obs, n, s)) return -1;
-    if (P->timing && P->sp_timer.end(s)) return -1;
+    if (!C->sp.work && sp_setup(C, src, obs, s)) return -1;
+    if (C->timing && C->sp_timer.begin(s)) return -1;
+    if (sp_launch(C, src, obs, n, s)) return -1;
+    if (C->timing && C->sp_timer.end(s)) return -1;
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+int mj_encode(MjPool* P, int agent, float* obs, uint8_t* masks, void* stream) {
+    if (!P) return fail("null pool");
+    if (!P->rows_valid) return fail("mj_rows_count must be called after mj_step and before mj_encode");
+    int n = P->last_rows[agent & 1];
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (wait_snapshot(P, s)) return -1;
+    return encode_launch(P, agent, pool_src(P, agent), n, obs, masks, s);
 }
 
 int mj_oracle_obs_rows(int version) {  // consts.rs:32-38
@@ -960,25 +975,30 @@ int mj_oracle_obs_rows(int version) {  // consts.rs:32-38
     return -1;
 }
 
+// The invisible obs of rows [0, n) of `src`, at `version`; all_yama: every undrawn yama tile is listed (replayed games)
+static int encode_oracle_launch(int version, const EncSrc& src, int n, float* out, int all_yama, hipStream_t s) {
+    OracleEncParams ep;
+    ep.rows = src.rows;
+    ep.n_rows = n;
+    ep.version = version;
+    ep.snap = src.snap;
+    ep.out = out;
+    ep.all_yama = all_yama;
+    size_t lds = enc_oracle_lds_bytes(ep.version);
+    if (ep.version == 1) hipLaunchKernelGGL(mj_k_encode_oracle<true>, dim3(n), dim3(ENC_THREADS), lds, s, ep);
+    else hipLaunchKernelGGL(mj_k_encode_oracle<false>, dim3(n), dim3(ENC_THREADS), lds, s, ep);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 int mj_encode_oracle(MjPool* P, int agent, float* out, void* stream) {
     if (!P) return fail("null pool");
     if (!P->rows_valid) return fail("mj_rows_count must be called after mj_step and before mj_encode_oracle");
     int n = P->last_rows[agent & 1];
     if (n == 0) return 0;
-    OracleEncParams ep;
-    ep.rows = P->rows[agent & 1].get();
-    ep.n_rows = n;
-    ep.version = P->version[agent & 1];
-    ep.snap = P->snap.get();
-    ep.out = out;
-    ep.all_yama = P->rp_active ? 1 : 0;
-    size_t lds = enc_oracle_lds_bytes(ep.version);
     hipStream_t s = (hipStream_t)stream;
     if (wait_snapshot(P, s)) return -1;
-    if (ep.version == 1) hipLaunchKernelGGL(mj_k_encode_oracle<true>, dim3(n), dim3(ENC_THREADS), lds, s, ep);
-    else hipLaunchKernelGGL(mj_k_encode_oracle<false>, dim3(n), dim3(ENC_THREADS), lds, s, ep);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return encode_oracle_launch(P->version[agent & 1], pool_src(P, agent), n, out, P->rp_active ? 1 : 0, s);
 }
 
 int mj_encode_timing(MjPool* P, int enable, double* total_ms, int64_t* launches) {
@@ -1556,6 +1576,159 @@ int mj_replay_load_harvest(MjPool* dst, const MjHarvest* h, int game0, const uin
     return replay_load_src("mj_replay_load_harvest", dst, harvest_log_src(h, game0, n),
                            SeedSrc{nullptr, 0, h->nonce.get() + game0, h->key.get() + game0}, tracked_host, always_include_kan_select,
                            flags, counts_out, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------- sample store (mj_samples.hip)
+struct MjSamples {
+    int64_t capacity = 0, count = 0;
+    int version = 0, batch_rows = 0;
+    DevBuf<TableOne> rec;    // [capacity] a sample's record ...
+    DevBuf<uint32_t> desc;   // ... its row descriptor without the table (seat, kan flag) ...
+    DevBuf<int32_t> meta;    // ... and its eight int32 of mj_k_replay_meta, [1] = the game number
+    // The indices of the encode call under way: copied to pinned memory (the caller's array may go when the call returns), from there
+    // to the device in one copy; ev_idx, recorded behind that copy, is what the next call waits for before it overwrites the pinned words.
+    DevBuf<int32_t> idx;     // [idx_cap]
+    PinnedBuf<int32_t> idx_pin;
+    Event ev_idx;
+    int idx_cap = 0;         // batch_rows at first, grown to the largest call
+    // The encode context: a pool of batch_rows tables that is never stepped.  The encode launches take from it what they take from
+    // a pool beside the records -- obs version, op-list flag, SP resources, knobs, timers -- and its rows[0] holds a chunk's descriptors.
+    std::unique_ptr<MjPool> ctx;
+    hipStream_t enc_stream = nullptr;  // the stream of the last encode: mj_samples_info reads the overflow words behind it
+};
+#define MJ_SAMPLES_MAX ((int64_t)ROW_TABLE(~0u))  // a sample's index is the ROW_TABLE field of its row: 2^28 - 1
+
+MjSamples* mj_samples_create(int64_t capacity, int version, int batch_rows) {
+    if (capacity < 1 || capacity > MJ_SAMPLES_MAX) {
+        fail("mj_samples_create: capacity " + std::to_string(capacity) + " is not in [1, " + std::to_string(MJ_SAMPLES_MAX) +
+             "] (a sample's index takes the 28 table bits of a row descriptor)");
+        return nullptr;
+    }
+    if (batch_rows < 1) {
+        fail("mj_samples_create: batch_rows must be at least 1");
+        return nullptr;
+    }
+    std::unique_ptr<MjSamples> S(new MjSamples);
+    S->ctx.reset(mj_pool_create(batch_rows, version, MJ_DEAL_RAND08, batch_rows));  // (refuses a bad version, missing tables)
+    if (!S->ctx) return nullptr;
+    if (S->rec.alloc((size_t)capacity) || S->desc.alloc((size_t)capacity) || S->meta.alloc((size_t)capacity * 8) ||
+        S->idx.alloc((size_t)batch_rows) || S->idx_pin.alloc((size_t)batch_rows) || S->ev_idx.create_no_timing())
+        return nullptr;
+    S->idx_cap = batch_rows;
+    S->capacity = capacity;
+    S->version = version;
+    S->batch_rows = batch_rows;
+    return S.release();
+}
+
+void mj_samples_destroy(MjSamples* S) { delete S; }
+
+int mj_samples_append(MjSamples* S, MjPool* P, int32_t log_base, void* stream) {
+    if (!S || !P) return fail("null store / pool");
+    if (!P->rp.script) return fail("mj_samples_append: the pool has no replay script (the label of a sample comes from it): mj_replay_load first");
+    if (!P->rows_valid) return fail("mj_rows_count must be called after mj_replay_step and before mj_samples_append");
+    const int n = P->last_rows[0];
+    if (n == 0) return 0;
+    if (S->count + n > S->capacity)
+        return fail("mj_samples_append: " + std::to_string(n) + " rows do not fit a store of " + std::to_string(S->capacity) +
+                    " samples that holds " + std::to_string(S->count));
+    hipStream_t s = (hipStream_t)stream;
+    if (wait_snapshot(P, s)) return -1;
+    const SamplesAppendParams ap = {P->snap.get(), P->blocks.get(), P->rows[0].get(), n, P->rp.label.get(), P->rp.kan_label.get(),
+                                    P->rp.kyoku.get(), P->rp.ev_index.get(), log_base, S->rec.get() + S->count,
+                                    S->desc.get() + S->count, S->meta.get() + S->count * 8};
+    hipLaunchKernelGGL(mj_k_samples_append, dim3(n), dim3(64), 0, s, ap);
+    HIP_OK(hipGetLastError());
+    S->count += n;
+    return 0;
+}
+
+int mj_samples_truncate(MjSamples* S, int64_t count) {
+    if (!S) return fail("null store");
+    if (count < 0 || count > S->count)
+        return fail("mj_samples_truncate: " + std::to_string(count) + " is not in [0, " + std::to_string(S->count) + "]");
+    S->count = count;
+    return 0;
+}
+
+int mj_samples_info(const MjSamples* S, int64_t out[4]) {
+    if (!S || !out) return fail("null store / output");
+    out[0] = S->count, out[1] = S->capacity, out[2] = (int64_t)(sizeof(TableOne) + sizeof(uint32_t) + 8 * sizeof(int32_t)), out[3] = 0;
+    HIP_OK(hipStreamSynchronize(S->enc_stream));
+    int f = 0;
+    HIP_OK(hipMemcpy(&f, S->ctx->enc_flag.get(), sizeof f, hipMemcpyDeviceToHost));
+    out[3] = f;
+    if (S->ctx->sp.err) {
+        unsigned long long ov = 0;
+        HIP_OK(hipMemcpy(&ov, S->ctx->sp.err.get() + SP_ERR_OVERFLOW, sizeof ov, hipMemcpyDeviceToHost));
+        out[3] += (int64_t)ov;
+    }
+    return 0;
+}
+
+int mj_samples_meta(const MjSamples* S, int64_t first, int64_t n, int32_t* meta_host, void* stream) {
+    if (!S) return fail("null store");
+    if (first < 0 || n < 0 || first > S->count - n) return fail("mj_samples_meta: sample range out of bounds");
+    if (n == 0) return 0;
+    if (!meta_host) return fail("mj_samples_meta: null output");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OK(hipMemcpyAsync(meta_host, S->meta.get() + first * 8, (size_t)n * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+
+namespace {
+// Every index checked before anything is queued; then the indices to the device and per chunk of batch_rows: their descriptors into
+// the context's row list, `launch(source, rows of the chunk, first row of the chunk)`.
+int samples_chunks(const char* who, MjSamples* S, const int32_t* idx_host, int n, hipStream_t s,
+                   const std::function<int(const EncSrc&, int, int64_t)>& launch) {
+    if (!S) return fail("null store");
+    if (n < 0) return fail(std::string(who) + ": negative number of samples");
+    if (n == 0) return 0;
+    if (!idx_host) return fail(std::string(who) + ": null indices");
+    for (int i = 0; i < n; i++)
+        if (idx_host[i] < 0 || idx_host[i] >= S->count)
+            return fail(std::string(who) + ": index " + std::to_string(idx_host[i]) + " (position " + std::to_string(i) +
+                        ") is not in a store of " + std::to_string(S->count) + " samples");
+    HIP_OK(hipEventSynchronize(S->ev_idx.get()));  // the last call's copy out of the pinned words
+    if (n > S->idx_cap) {
+        DevBuf<int32_t> idx;
+        PinnedBuf<int32_t> pin;
+        if (idx.alloc((size_t)n) || pin.alloc((size_t)n)) return -1;
+        S->idx = std::move(idx);  // (the smaller pair goes with the locals; hipFree waits for the kernels that read it)
+        S->idx_pin = std::move(pin);
+        S->idx_cap = n;
+    }
+    memcpy(S->idx_pin.get(), idx_host, (size_t)n * sizeof(int32_t));
+    HIP_OK(hipMemcpyAsync(S->idx.get(), S->idx_pin.get(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_OK(hipEventRecord(S->ev_idx.get(), s));
+    uint32_t* rows = S->ctx->rows[0].get();
+    const EncSrc src = {S->rec.get(), rows};
+    S->enc_stream = s;
+    for (int64_t at = 0; at < n; at += S->batch_rows) {
+        const int k = (int)std::min<int64_t>(S->batch_rows, n - at);
+        hipLaunchKernelGGL(mj_k_samples_rows, dim3((k + 255) / 256), dim3(256), 0, s, S->idx.get() + at, S->desc.get(), k, rows);
+        HIP_OK(hipGetLastError());
+        if (launch(src, k, at)) return -1;
+    }
+    return 0;
+}
+}  // namespace
+
+int mj_samples_encode(MjSamples* S, const int32_t* idx_host, int n, float* obs, uint8_t* masks, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const size_t row = S ? (size_t)mj_obs_rows(S->version) * 34 : 0;
+    return samples_chunks("mj_samples_encode", S, idx_host, n, s, [&](const EncSrc& src, int k, int64_t at) {
+        return encode_launch(S->ctx.get(), 0, src, k, obs + (size_t)at * row, masks + (size_t)at * 46, s);
+    });
+}
+
+int mj_samples_encode_oracle(MjSamples* S, const int32_t* idx_host, int n, float* out, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const size_t row = S ? (size_t)mj_oracle_obs_rows(S->version) * 34 : 0;
+    return samples_chunks("mj_samples_encode_oracle", S, idx_host, n, s, [&](const EncSrc& src, int k, int64_t at) {
+        return encode_oracle_launch(S->version, src, k, out + (size_t)at * row, 1 /* the sources are replay pools */, s);
+    });
 }
 
 __global__ void mj_k_first_error(const TableBlock* blocks, int n_tables, unsigned long long* out) {

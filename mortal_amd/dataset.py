@@ -406,11 +406,29 @@ class GameplayLoader:
         harvest._handle()  # (a closed Harvest is refused before anything else)
         return self._load_device(harvest, game0, n_games, seats, names, augmented)
 
-    def _load_device(self, src, first, count, seats, names, augmented):
-        """load_pool / load_harvest: logs [first, first + count) of a device source -> the Gameplays.  `src` is a TablePool or a
-        Harvest: n_logs, log_units / log_where (what the messages call it), pool_cls, device, deal_algo, log_cap, grp(first, n)
-        -> the Grps (None = skipped); the replay pool loads its scripts from it (TablePool.replay_load_<log_where>)."""
-        who, unit, where, n_src = f"load_{src.log_where}", src.log_units, src.log_where, src.n_logs
+    def store_pool(self, pool, table0=0, n_tables=None, seats=None, names=None, augmented=False, store=None, capacity=None,
+                   batch_rows=1024):
+        """load_pool into a SampleStore (mortal_amd/samples.py): the same tables, refusals, seat / name / skip semantics and
+        `augmented` keyword, but every decision is kept as its 2 KB record instead of its obs, and no encoder or SP kernel runs
+        until a batch is drawn (store.encode).  -> the store.
+
+        store: append to this store (its games are numbered on from len(store.grps)) -- how successive pools or harvests fill one
+        buffer; None: a new one of `capacity` samples (default 4,096 per table of the call) and `batch_rows` rows per encode launch.
+        On any failure -- the capacity, an illegal log -- the caller's store is back at its count and games on entry.  With
+        oracle=True the walls are dealt from the seeds and store.encode_oracle gives the invisible obs."""
+        return self._store_device(pool, table0, n_tables, seats, names, augmented, store, capacity, batch_rows)
+
+    def store_harvest(self, harvest, game0=0, n_games=None, seats=None, names=None, augmented=False, store=None, capacity=None,
+                      batch_rows=1024):
+        """load_harvest into a SampleStore, as store_pool: games [game0, game0 + n_games) of the harvest's sorted order."""
+        harvest._handle()
+        return self._store_device(harvest, game0, n_games, seats, names, augmented, store, capacity, batch_rows)
+
+    def _device_games(self, who, src, first, count, seats, names):
+        """What load_* and store_* check and prepare: logs [first, first + count) of a device source -> (n, per log dict(names,
+        wanted, grp), tracked seat masks).  `src` is a TablePool or a Harvest: n_logs, log_units / log_where (what the messages
+        call it), pool_cls, device, deal_algo, log_cap, grp(first, n) -> the Grps (None = skipped)."""
+        unit, where, n_src = src.log_units, src.log_where, src.n_logs
         if self.augmented:
             raise ValueError(f"{who}: a loader constructed with augmented=True is not accepted here (a pool or a harvest is read in "
                              f"both forms by one loader): construct it without and pass {who}(..., augmented=True) per call")
@@ -418,7 +436,7 @@ class GameplayLoader:
         if first < 0 or n < 0 or first + n > n_src:
             raise ValueError(f"{who}: {unit} [{first}, {first + n}) are not in a {where} of {n_src}")
         if n == 0:
-            return []
+            return 0, [], []
         masks = np.full(n, 15, dtype=np.uint8) if seats is None else np.ascontiguousarray(seats, dtype=np.uint8)
         if masks.shape != (n,):
             raise ValueError(f"seats: expected {n} masks, got shape {masks.shape}")
@@ -430,16 +448,67 @@ class GameplayLoader:
             nm = list(names[t]) if names is not None else ["", "", "", ""]
             wanted = [p for p in (self._wanted(nm) if names is not None else range(4)) if (int(masks[t]) >> p) & 1]
             games.append(dict(names=nm, wanted=wanted if grps[t] is not None else [], grp=grps[t]))
-        tracked = [sum(1 << p for p in g["wanted"]) for g in games]
+        return n, games, [sum(1 << p for p in g["wanted"]) for g in games]
+
+    def _replay_device(self, src, first, n, tracked, augmented, body):
+        """body(replay pool) over a pool that has loaded logs [first, first + n) of `src` as its scripts
+        (TablePool.replay_load_<log_where>)."""
         rp = src.pool_cls(n, version=self.version, device=str(src.device), max_rows=8 * n + 64, deal_algo=src.deal_algo)
         try:
-            load = getattr(rp, f"replay_load_{where}")  # TablePool.replay_load_pool / replay_load_harvest
+            load = getattr(rp, f"replay_load_{src.log_where}")  # TablePool.replay_load_pool / replay_load_harvest
             load(src, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle, augmented=augmented)
-            # every step applies at least one event of every unfinished log, and an event takes at least one word
-            samples = self._replay_samples(rp, n, src.log_cap + 8, first)
+            return body(rp)
         finally:
             rp.close()
+
+    def _load_device(self, src, first, count, seats, names, augmented):
+        """load_pool / load_harvest: logs [first, first + count) of a device source -> the Gameplays."""
+        n, games, tracked = self._device_games(f"load_{src.log_where}", src, first, count, seats, names)
+        if n == 0:
+            return []
+        # every step applies at least one event of every unfinished log, and an event takes at least one word
+        samples = self._replay_device(src, first, n, tracked, augmented,
+                                      lambda rp: self._replay_samples(rp, n, src.log_cap + 8, first))
         return self._slice_gameplays(games, *samples)
+
+    def _store_device(self, src, first, count, seats, names, augmented, store, capacity, batch_rows):
+        """store_pool / store_harvest: _load_device with store.append in the place of encode / encode_oracle / replay_meta."""
+        from .samples import SampleStore
+
+        who = f"store_{src.log_where}"
+        n, games, tracked = self._device_games(who, src, first, count, seats, names)
+        own = store is None
+        if own:
+            store = SampleStore(4096 * max(n, 1) if capacity is None else capacity, self.version, batch_rows=batch_rows,
+                                device=str(src.device), lib=src._L)
+        else:
+            store._handle()
+            if store.version != self.version or store._L is not src._L:
+                raise ValueError(f"{who}: the store holds obs v{store.version} samples of "
+                                 f"{'another' if store._L is not src._L else 'the same'} library, the loader reads v{self.version}")
+        mark = store._mark()
+        game0 = len(store.grps)
+
+        def fill(rp):
+            for _ in range(src.log_cap + 8):
+                if rp.replay_step():
+                    store.append(rp, game0)
+                elif rp.counters()["games"] >= n:
+                    break
+            else:
+                raise RuntimeError("log replay did not terminate")
+            code, tbl = rp.first_error()
+            if code:
+                raise ValueError(f"log {first + tbl}: the event stream is not a legal game (error code {code})")
+
+        try:
+            if n:
+                self._replay_device(src, first, n, tracked, augmented, fill)
+            store._add_games(games, self.oracle)
+        except BaseException:
+            store.close() if own else store._rollback(mark)
+            raise
+        return store
 
     def _replay_samples(self, pool, n, max_steps, table0=0):
         """The replay loop over a loaded pool -> (obs, masks, meta, invisible obs or None), every sample of every tracked seat in
