@@ -13,10 +13,9 @@ import gzip
 import json
 
 import numpy as np
-import torch
 
 from . import _lib, mjai_log
-from .pool import ACTION_SPACE, OBS_ROWS, TablePool
+from .pool import OBS_ROWS, TablePool
 
 GRP_SIZE = 7
 
@@ -365,14 +364,12 @@ class GameplayLoader:
                     walls = self._walls_from_events(g["events"], self.augmented, rng)
                     scripts.append(mjai_log.encode_events(g["events"], augmented=self.augmented, walls=walls))
         tracked = [sum(1 << p for p in g["wanted"]) for g in games]
-        total_events = sum(len(g["events"]) for g in games)
-        pool = self.pool_cls(n, version=self.version, device=self.device, max_rows=8 * n + 64, deal_algo=self.deal_algo)
-        try:
-            pool.replay_load(scripts, tracked, self.always_include_kan_select, nonces, keys)
-            samples = self._replay_samples(pool, n, total_events + 8)
-        finally:
-            pool.close()
-        return self._slice_gameplays(games, *samples)
+
+        def fill(store):
+            self._replay(store, self.pool_cls, self.device, self.deal_algo, n, lambda rp: rp.replay_load(
+                scripts, tracked, self.always_include_kan_select, nonces, keys), sum(len(g["events"]) for g in games) + 8)
+
+        return self._load(games, tracked, [len(s) for s in scripts], self.device, self.pool_cls._L, fill)
 
     def load_pool(self, pool, table0=0, n_tables=None, seats=None, names=None, augmented=False):
         """The samples of a pool's finished games straight from its device log (TablePool.enable_log), without JSON or files:
@@ -392,8 +389,12 @@ class GameplayLoader:
         oracle=True the invisible obs follows the reference's mix, as load_logs does: events swapped, wall as the seed deals it.
         A loader constructed with augmented=True is refused here (ValueError): pass the keyword instead.
 
-        Memory: all obs of the range are materialised on the device at once (137 KB per obs-v4 sample, about 600 samples per
-        game and seat), so the caller bounds memory by the table range it asks for."""
+        Memory: all obs of the range are materialised on the device at once (137 KB per obs-v4 sample, about 220 samples per
+        game and seat), so the caller bounds memory by the table range it asks for.  At the peak that one copy, written in the
+        reference's order, is resident beside the records of the replay, 2,148 B for each of sample_bound's samples: 1.9 GB
+        beside 7.2 GB of obs v3 for all seats of 64 self-play games, 10.5 beside 29.5 GB for one seat of 1,024.  (Until the
+        loaders went through the store, the obs of the replay steps, their concatenation and then its reordered copy were
+        resident two at a time: 14.3 and 59.1 GB.)"""
         return self._load_device(pool, table0, n_tables, seats, names, augmented)
 
     def load_harvest(self, harvest, game0=0, n_games=None, seats=None, names=None, augmented=False):
@@ -427,7 +428,7 @@ class GameplayLoader:
     def _device_games(self, who, src, first, count, seats, names):
         """What load_* and store_* check and prepare: logs [first, first + count) of a device source -> (n, per log dict(names,
         wanted, grp), tracked seat masks).  `src` is a TablePool or a Harvest: n_logs, log_units / log_where (what the messages
-        call it), pool_cls, device, deal_algo, log_cap, grp(first, n) -> the Grps (None = skipped)."""
+        call it), pool_cls, device, deal_algo, log_cap, log_words(first, n), grp(first, n) -> the Grps (None = skipped)."""
         unit, where, n_src = src.log_units, src.log_where, src.n_logs
         if self.augmented:
             raise ValueError(f"{who}: a loader constructed with augmented=True is not accepted here (a pool or a harvest is read in "
@@ -450,29 +451,62 @@ class GameplayLoader:
             games.append(dict(names=nm, wanted=wanted if grps[t] is not None else [], grp=grps[t]))
         return n, games, [sum(1 << p for p in g["wanted"]) for g in games]
 
-    def _replay_device(self, src, first, n, tracked, augmented, body):
-        """body(replay pool) over a pool that has loaded logs [first, first + n) of `src` as its scripts
-        (TablePool.replay_load_<log_where>)."""
-        rp = src.pool_cls(n, version=self.version, device=str(src.device), max_rows=8 * n + 64, deal_algo=src.deal_algo)
+    def _replay(self, store, pool_cls, device, deal_algo, n, load, max_steps, first=0):
+        """The one way from logs to samples: a replay pool of n tables takes its scripts from `load(pool)`, and every decision of
+        every step becomes a record of `store`, its games numbered on from len(store.grps).  first = what the messages call the
+        pool's table 0."""
+        rp = pool_cls(n, version=self.version, device=device, max_rows=8 * n + 64, deal_algo=deal_algo)
         try:
-            load = getattr(rp, f"replay_load_{src.log_where}")  # TablePool.replay_load_pool / replay_load_harvest
-            load(src, first, tracked, self.always_include_kan_select, deal_from_seed=self.oracle, augmented=augmented)
-            return body(rp)
+            load(rp)
+            game0 = len(store.grps)
+            for _ in range(max_steps):
+                if rp.replay_step():
+                    store.append(rp, game0)
+                elif rp.counters()["games"] >= n:
+                    break
+            else:
+                raise RuntimeError("log replay did not terminate")
+            code, tbl = rp.first_error()
+            if code:
+                raise ValueError(f"log {first + tbl}: the event stream is not a legal game (error code {code})")
         finally:
             rp.close()
+
+    def _replay_device(self, store, src, first, n, tracked, augmented):
+        """_replay of logs [first, first + n) of a device source (TablePool.replay_load_pool / replay_load_harvest)."""
+        def load(rp):
+            getattr(rp, f"replay_load_{src.log_where}")(src, first, tracked, self.always_include_kan_select,
+                                                        deal_from_seed=self.oracle, augmented=augmented)
+        # every step applies at least one event of every unfinished log, and an event takes at least one word
+        self._replay(store, src.pool_cls, str(src.device), src.deal_algo, n, load, src.log_cap + 8, first)
+
+    def _load(self, games, tracked, words, device, lib, fill):
+        """load_logs / load_pool / load_harvest: `fill(store)` replays the games into a store of this call's own, sized by
+        sample_bound and so never refused for its size; its Gameplays, encoded once and in the reference's order, are all that
+        is left of it."""
+        from .samples import MAX_CAPACITY, SampleStore
+
+        store = SampleStore(min(max(sample_bound(tracked, words), 1), MAX_CAPACITY), self.version,
+                            batch_rows=load_batch_rows(len(games)), device=device, lib=lib)
+        try:
+            fill(store)
+            store._add_games(games, self.oracle)
+            out = store.gameplays(invisible=self.oracle)
+            store.check_overflow(RuntimeError("obs v4: a sample's single-player state graph exceeded the device scratch capacity"))
+            return out
+        finally:
+            store.close()
 
     def _load_device(self, src, first, count, seats, names, augmented):
         """load_pool / load_harvest: logs [first, first + count) of a device source -> the Gameplays."""
         n, games, tracked = self._device_games(f"load_{src.log_where}", src, first, count, seats, names)
         if n == 0:
             return []
-        # every step applies at least one event of every unfinished log, and an event takes at least one word
-        samples = self._replay_device(src, first, n, tracked, augmented,
-                                      lambda rp: self._replay_samples(rp, n, src.log_cap + 8, first))
-        return self._slice_gameplays(games, *samples)
+        return self._load(games, tracked, src.log_words(first, n), str(src.device), src._L,
+                          lambda store: self._replay_device(store, src, first, n, tracked, augmented))
 
     def _store_device(self, src, first, count, seats, names, augmented, store, capacity, batch_rows):
-        """store_pool / store_harvest: _load_device with store.append in the place of encode / encode_oracle / replay_meta."""
+        """store_pool / store_harvest: _load_device into the caller's store, or a new one that is handed over."""
         from .samples import SampleStore
 
         who = f"store_{src.log_where}"
@@ -487,92 +521,32 @@ class GameplayLoader:
                 raise ValueError(f"{who}: the store holds obs v{store.version} samples of "
                                  f"{'another' if store._L is not src._L else 'the same'} library, the loader reads v{self.version}")
         mark = store._mark()
-        game0 = len(store.grps)
-
-        def fill(rp):
-            for _ in range(src.log_cap + 8):
-                if rp.replay_step():
-                    store.append(rp, game0)
-                elif rp.counters()["games"] >= n:
-                    break
-            else:
-                raise RuntimeError("log replay did not terminate")
-            code, tbl = rp.first_error()
-            if code:
-                raise ValueError(f"log {first + tbl}: the event stream is not a legal game (error code {code})")
-
         try:
             if n:
-                self._replay_device(src, first, n, tracked, augmented, fill)
+                self._replay_device(store, src, first, n, tracked, augmented)
             store._add_games(games, self.oracle)
         except BaseException:
             store.close() if own else store._rollback(mark)
             raise
         return store
 
-    def _replay_samples(self, pool, n, max_steps, table0=0):
-        """The replay loop over a loaded pool -> (obs, masks, meta, invisible obs or None), every sample of every tracked seat in
-        the order the device produced them."""
-        obs_parts, mask_parts, meta_parts, inv_parts = [], [], [], []
-        for _ in range(max_steps):
-            k = pool.replay_step()
-            if k == 0:
-                if pool.counters()["games"] >= n:
-                    break
-                continue
-            obs, masks = pool.encode(0)
-            obs_parts.append(obs)
-            mask_parts.append(masks)
-            meta_parts.append(pool.replay_meta())
-            if self.oracle:
-                inv_parts.append(pool.encode_oracle(0))
-        else:
-            raise RuntimeError("log replay did not terminate")
-        code, tbl = pool.first_error()
-        if code:
-            raise ValueError(f"log {table0 + tbl}: the event stream is not a legal game (error code {code})")
-        pool.check_sp_overflow(RuntimeError("obs v4: a sample's single-player state graph exceeded the device scratch capacity"))
-        if obs_parts:
-            obs = torch.cat(obs_parts)
-            masks = torch.cat(mask_parts)
-            meta = torch.cat(meta_parts).cpu().numpy()
-        else:
-            obs = torch.empty((0, OBS_ROWS[self.version], 34), dtype=torch.float32, device=pool.device)
-            masks = torch.empty((0, ACTION_SPACE), dtype=torch.bool, device=pool.device)
-            meta = np.zeros((0, 8), dtype=np.int32)
-        return obs, masks, meta, (torch.cat(inv_parts) if (self.oracle and inv_parts) else None)
 
-    @staticmethod
-    def _slice_gameplays(games, obs, masks, meta, inv):
-        """games: per log dict(names, wanted, grp) -> list (per log) of lists of Gameplay (one per wanted seat)."""
-        # order the samples of every (log, seat) like the reference: by event, the kan-select entry after its main entry
-        order = np.lexsort((meta[:, 6], meta[:, 7], meta[:, 2], meta[:, 1])) if len(meta) else np.zeros(0, dtype=np.int64)
-        meta = meta[order]
-        idx_dev = torch.as_tensor(order, device=obs.device, dtype=torch.long)
-        obs, masks = obs[idx_dev], masks[idx_dev]
-        inv = inv[idx_dev].cpu().numpy() if inv is not None else None
-        out = []
-        pos = 0
-        for t, g in enumerate(games):
-            per_log = []
-            for p in g["wanted"]:
-                lo = pos
-                while pos < len(meta) and meta[pos, 1] == t and meta[pos, 2] == p:
-                    pos += 1
-                m = meta[lo:pos]
-                gp = Gameplay(p, g["names"][p], Grp(g["grp"].feature.copy(), g["grp"].rank_by_player, g["grp"].final_scores))
-                gp.obs_dev = obs[lo:pos]
-                gp.masks_dev = masks[lo:pos]
-                if inv is not None:
-                    gp.invisible_obs = list(inv[lo:pos])
-                gp.actions = [int(x) for x in m[:, 0]]
-                gp.at_kyoku = [int(x) for x in m[:, 3]]
-                gp.at_turns = [int(x) for x in m[:, 4]]
-                gp.shantens = [int(x) for x in m[:, 5]]
-                gp.apply_gamma = [bool(x <= 37) for x in m[:, 0]]  # only discard and kan will discount (gameplay.rs:423)
-                ak = gp.at_kyoku
-                gp.dones = [ak[i + 1] > ak[i] for i in range(len(ak) - 1)] + [True]  # gameplay.rs:264-265
-                per_log.append(gp)
-            out.append(per_log)
-        assert pos == len(meta)
-        return out
+def load_batch_rows(n):
+    """Rows per encode launch of the store behind a load_* of n games.  For obs v4 the encode context sizes the SP work areas
+    (mj_capi.hip sp_setup: min(1024, r) + spare + wide areas of 8.1 MB, spare = max(8, t / 4) rounded down to even, at most
+    512, wide = max(2, t / 16), at most 256) from its t = r = batch_rows, where the replay pool of a load sized them from
+    t = n, r = 8 n + 64.  This rule never takes more areas than that did: 69 for 82 at n = 1, 567 for 596 at n = 64, 850 for
+    894 at n = 100, and from n = 120 on 1,008 for 1,061 and more."""
+    return min(768, 6 * n + 48)
+
+
+def sample_bound(tracked, words):
+    """The most samples a replay can give: tracked = the 4-bit seat mask of every log, words = its length in script words.
+    mj_k_replay gives rows only after it applied an event, every event is at least one word, and an applied event gives a tracked
+    seat that can act one main row and at most one kan-select row.  Every event handler first clears all four seats' `cans`
+    (ev_prologue) and then sets them for the actor alone (tsumo, chi / pon, reach) or for the other three (dahai, the chankan of
+    kakan): at most min(tracked seats, 3) seats act, whatever the words say, so a log gives at most 2 * min(popcount(tracked), 3)
+    samples per word.  (A legal game stays within min(4, popcount + 1) per event, since only the seat that declares the kan gets
+    a select row -- tests/loader_cases.py counts that on the reference's side.  The replay labels an event before it knows whether
+    the next one is legal: behind a discard, a kakan or ankan word would give every caller a select row, hence the wider bound.)"""
+    return sum(2 * min(bin(int(t)).count("1"), 3) * int(w) for t, w in zip(tracked, words))

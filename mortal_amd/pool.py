@@ -119,6 +119,9 @@ class Harvest:
         n = self.n_games - game0 if n is None else n
         return _grp_call(self._L, self._L.mj_harvest_grp, (self._handle(), int(game0)), n, max_kyoku, "game", game0)[0]
 
+    def log_words(self, first, n):
+        return self.games["n_words"][first:first + n]
+
 
 class TablePool:
     _L = lib  # the C-ABI library (tests/host/emu_pool.py substitutes the host emulation of the same sources)
@@ -229,6 +232,10 @@ class TablePool:
 
     def grp(self, first=0, n=None, max_kyoku=64):
         return self.log_grp(first, n, max_kyoku)
+
+    def log_words(self, first, n):
+        """The script words logs [first, first + n) have at most: mj_k_log_pack copies a log at its own length, never past log_cap."""
+        return np.minimum(self.log_lengths()[first:first + n], self.log_cap)
 
     def _handle(self):
         return self.h

@@ -1,10 +1,12 @@
 """SampleStore: replayed decisions kept on the device as records, encoded in batches on demand (include/mortal_amd.h mj_samples_*).
 
 The reference's data loader keeps every obs of a batch of files in a buffer and shuffles it (mortal/dataloader.py:45-113
-populate_buffer + random.shuffle).  `GameplayLoader.load_pool` / `load_harvest` do the same on the device, at 127 to 138 KB per
-sample.  The encoders read nothing of a decision but its snapshot record (about 2 KB) and a row descriptor, so a store keeps those
-with the sample's bookkeeping and runs the unchanged obs / mask / SP kernels over any list of its samples: what stays resident is
-1/58 of the obs, and only the samples a batch draws are ever encoded.  `GameplayLoader.store_pool` / `store_harvest` fill a store.
+populate_buffer + random.shuffle), at 127 to 138 KB per sample.  The encoders read nothing of a decision but its snapshot record
+(about 2 KB) and a row descriptor, so a store keeps those with the sample's bookkeeping and runs the unchanged obs / mask / SP
+kernels over any list of its samples: what stays resident is 1/58 of the obs, and only the samples a batch draws are ever encoded.
+A store is the one way from a replayed log to a sample: `GameplayLoader.store_pool` / `store_harvest` fill one and hand it over;
+`load_logs` / `load_pool` / `load_harvest` fill one of their own, take `gameplays()` of it -- every obs of the range, encoded once
+and in the reference's order -- and close it.
 """
 import numpy as np
 import torch
@@ -134,7 +136,8 @@ class SampleStore:
 
     @property
     def order(self):
-        """The permutation that puts the samples in the reference's order (the lexsort of GameplayLoader._slice_gameplays)."""
+        """The permutation that puts the samples in the reference's order: by game, seat, event, the kan-select entry behind its
+        main entry (gameplay.rs:239-443 walks one player's events in order)."""
         m = self.meta
         return self._cached("order", lambda: np.lexsort((m[:, 6], m[:, 7], m[:, 2], m[:, 1])).astype(np.int64))
 
@@ -177,12 +180,14 @@ class SampleStore:
             return before[end] - before[:n]
         return self._cached("steps_to_done", make)
 
+    def _bounds(self, game, seat):
+        """The positions [lo, hi) of one Gameplay (game, seat) in the reference's order."""
+        key = self._cached("key", lambda: self._sorted()[:, 1].astype(np.int64) * 4 + self._sorted()[:, 2])
+        return np.searchsorted(key, [game * 4 + seat, game * 4 + seat + 1])
+
     def span(self, game, seat):
         """The store indices of one Gameplay (game, seat), in the reference's order."""
-        m = self._sorted()
-        key = m[:, 1].astype(np.int64) * 4 + m[:, 2]
-        lo, hi = np.searchsorted(key, [game * 4 + seat, game * 4 + seat + 1])
-        return self.order[lo:hi]
+        return self.order[slice(*self._bounds(game, seat))]
 
     # ---- encoding
     def _indices(self, idx):
@@ -225,32 +230,44 @@ class SampleStore:
         L.check(L.mj_samples_encode_oracle(h, a.ctypes.data, n, out.data_ptr(), L.stream()))
         return out[:n]
 
-    def check_overflow(self):
-        """Raise when an encode of this store overflowed the encoder's op list or the SP kernel's scratch (its rows are incomplete)."""
+    def check_overflow(self, error=None):
+        """Raise (`error`, when given) when an encode of this store overflowed the encoder's op list or the SP kernel's scratch
+        (its rows are incomplete)."""
         if self._info()[3]:
-            raise MortalAmdError("SampleStore: an encoded sample overflowed the encoder's op list or, for obs v4, its single-player "
-                                 "state graph exceeded the device scratch capacity (SP_CAP in mortal_amd/csrc/mj_sp.hip)")
+            raise error or MortalAmdError("SampleStore: an encoded sample overflowed the encoder's op list or, for obs v4, its "
+                                          "single-player state graph exceeded the device scratch capacity (SP_CAP in mortal_amd/csrc/mj_sp.hip)")
 
-    def gameplay(self, game, seat, invisible=None):
-        """One Gameplay as GameplayLoader.load_pool returns it, its obs, masks (and invisible obs: default = the store has the
-        walls) encoded now from span(game, seat)."""
+    def _build(self, pairs, lo, hi, invisible):
+        """The Gameplays (gameplay.rs:46-64) of `pairs` (game, seat), all within positions [lo, hi) of the reference's order:
+        that range is encoded once, each Gameplay takes its slice."""
         from .dataset import Gameplay, Grp
 
+        obs, masks = self.encode(self.order[lo:hi])
+        inv = self.encode_oracle(self.order[lo:hi]).cpu().numpy() if (self.has_walls if invisible is None else invisible) else None
+        cols = [getattr(self, c) for c in ("actions", "at_kyoku", "at_turns", "shantens", "apply_gamma", "dones")]
+        out = []
+        for game, seat in pairs:
+            a, b = self._bounds(game, seat)
+            g = self.grps[game]
+            gp = Gameplay(seat, self.names[game][seat], Grp(g.feature.copy(), g.rank_by_player, g.final_scores))
+            gp.obs_dev, gp.masks_dev = obs[a - lo:b - lo], masks[a - lo:b - lo]
+            if inv is not None:
+                gp.invisible_obs = list(inv[a - lo:b - lo])
+            gp.actions, gp.at_kyoku, gp.at_turns, gp.shantens, gp.apply_gamma, gp.dones = (c[a:b].tolist() for c in cols)
+            gp.dones = gp.dones or [True]  # (the reference's list ends in True even when it is empty: gameplay.rs:264-265)
+            out.append(gp)
+        return out
+
+    def gameplays(self, invisible=None):
+        """What GameplayLoader.load_pool returns: a list per game of Gameplay, one per wanted seat (none for a skipped game), their
+        obs, masks (and invisible obs: default = the store has the walls) encoded now, once, in the reference's order."""
+        self._handle()
+        built = iter(self._build([(g, p) for g, seats in enumerate(self.wanted) for p in seats], 0, self.count, invisible))
+        return [[next(built) for _ in seats] for seats in self.wanted]
+
+    def gameplay(self, game, seat, invisible=None):
+        """One Gameplay of gameplays(), encoded from span(game, seat) alone."""
         self._handle()
         if not 0 <= game < len(self.grps) or self.grps[game] is None or seat not in self.wanted[game]:
             raise ValueError(f"SampleStore.gameplay: the store has no Gameplay of game {game}, seat {seat}")
-        g = self.grps[game]
-        idx = self.span(game, seat)
-        m = self.meta[idx]
-        gp = Gameplay(seat, self.names[game][seat], Grp(g.feature.copy(), g.rank_by_player, g.final_scores))
-        gp.obs_dev, gp.masks_dev = self.encode(idx)
-        if self.has_walls if invisible is None else invisible:
-            gp.invisible_obs = list(self.encode_oracle(idx).cpu().numpy())
-        gp.actions = [int(x) for x in m[:, 0]]
-        gp.at_kyoku = [int(x) for x in m[:, 3]]
-        gp.at_turns = [int(x) for x in m[:, 4]]
-        gp.shantens = [int(x) for x in m[:, 5]]
-        gp.apply_gamma = [bool(x <= 37) for x in m[:, 0]]
-        ak = gp.at_kyoku
-        gp.dones = [ak[i + 1] > ak[i] for i in range(len(ak) - 1)] + [True]
-        return gp
+        return self._build([(game, seat)], *self._bounds(game, seat), invisible)[0]

@@ -21,6 +21,8 @@ HOST = os.path.join(HERE, "host")
 if HOST not in sys.path:
     sys.path.insert(0, HOST)
 
+from emu_alloc import stats  # noqa: E402
+
 N = 4            # tables of every pool here
 CYCLES = 6       # of the scenario: the deal and five rounds of decisions, every row through mj_k_sp (or the small-pool schedule)
 REPLAY_STEPS = 8
@@ -43,12 +45,6 @@ def emu():
 def small_sp_work_areas(monkeypatch):
     monkeypatch.setenv("MJ_SP_GRID", "1")
     monkeypatch.setenv("MJ_SP_WIDE", "0")
-
-
-def stats(L):
-    out = (C.c_uint64 * 6)()
-    L.mj_emu_alloc_stats(out)
-    return dict(live=(out[0], out[1], out[2]), bad_frees=out[3], alloc=out[4], sync=out[5])
 
 
 def arm(L, kind=None, k=0):

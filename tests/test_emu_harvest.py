@@ -15,6 +15,7 @@ HOST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host")
 if HOST not in sys.path:
     sys.path.insert(0, HOST)
 
+from emu_alloc import first_samples as _first_samples, stats as _stats  # noqa: E402
 import harvest_cases as H  # noqa: E402
 import pool_gameplay_cases as G  # noqa: E402
 
@@ -114,22 +115,6 @@ def test_self_play_runner_refuses_mjai_log_engines(emu):
 
 
 # ---- allocation and synchronise failures of mj_harvest_take and mj_replay_load_harvest (as test_replay_load_pool_allocation_failures)
-def _stats(L):
-    out = (C.c_uint64 * 6)()
-    L.mj_emu_alloc_stats(out)
-    return dict(live=(out[0], out[1], out[2]), bad_frees=out[3], alloc=out[4], sync=out[5])
-
-
-def _first_samples(pool, steps=8):
-    out = []
-    for _ in range(steps):
-        if pool.replay_step():
-            obs, masks = pool.encode(0)
-            out += [pool.rows(0).tobytes(), obs.numpy().tobytes(), masks.numpy().tobytes(), pool.replay_meta().numpy().tobytes()]
-    assert len(out) >= 4
-    return b"".join(out)
-
-
 @pytest.mark.parametrize("deal_from_seed", [False, True])
 def test_replay_load_harvest_allocation_failures(emu, played, deal_from_seed):
     """For every allocation and every synchronise the call makes: the call fails, nothing is freed twice, the destination still

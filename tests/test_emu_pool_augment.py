@@ -1,7 +1,6 @@
 """Suit augmentation on the device (mj_k_log_pack<true> behind MJ_LOAD_AUGMENT and mj_augment_logs; GameplayLoader.load_pool /
 load_harvest(..., augmented=True), mjai_log.augment_logs), run on the host emulation of the device code.  The cases and their
 yardsticks live in tests/pool_augment_cases.py, shared with the `-m gpu` leg (tests/test_gpu_pool_augment.py)."""
-import ctypes as C
 import gc
 import os
 import shutil
@@ -14,6 +13,7 @@ HOST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host")
 if HOST not in sys.path:
     sys.path.insert(0, HOST)
 
+from emu_alloc import stats as _stats  # noqa: E402
 import pool_augment_cases as A  # noqa: E402
 import pool_gameplay_cases as G  # noqa: E402
 
@@ -66,12 +66,6 @@ def test_refusals_leave_the_destination_usable(emu, played):
 
 
 # ---- allocation and synchronise failures (as tests/test_emu_pool_gameplay.py sweeps the plain load)
-def _stats(L):
-    out = (C.c_uint64 * 6)()
-    L.mj_emu_alloc_stats(out)
-    return dict(live=(out[0], out[1], out[2]), bad_frees=out[3], alloc=out[4], sync=out[5])
-
-
 def _sweep(L, made):
     for kind in made:
         for k in range(1, made[kind] + 1):

@@ -1,7 +1,6 @@
 """Training samples and Grp from a pool's device log (mortal_amd/csrc/mj_gameplay.hip behind mj_replay_load_pool / mj_pool_grp /
 mj_grp_logs; GameplayLoader.load_pool, TablePool.log_grp, Grp.from_packed), run on the host emulation of the device code.  The
 cases and their yardsticks live in tests/pool_gameplay_cases.py, shared with the `-m gpu` leg."""
-import ctypes as C
 import gc
 import os
 import shutil
@@ -14,6 +13,7 @@ HOST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host")
 if HOST not in sys.path:
     sys.path.insert(0, HOST)
 
+from emu_alloc import first_samples as _first_samples, stats as _stats  # noqa: E402
 import pool_gameplay_cases as G  # noqa: E402
 
 
@@ -105,22 +105,6 @@ def test_batch_runner_gameplays(oracle, emu):
 
 
 # ---- allocation and synchronise failures in mj_replay_load_pool (as tests/test_emu_alloc_failures.py sweeps the other calls)
-def _stats(L):
-    out = (C.c_uint64 * 6)()
-    L.mj_emu_alloc_stats(out)
-    return dict(live=(out[0], out[1], out[2]), bad_frees=out[3], alloc=out[4], sync=out[5])
-
-
-def _first_samples(pool, steps=8):
-    out = []
-    for _ in range(steps):
-        if pool.replay_step():
-            obs, masks = pool.encode(0)
-            out += [pool.rows(0).tobytes(), obs.numpy().tobytes(), masks.numpy().tobytes(), pool.replay_meta().numpy().tobytes()]
-    assert len(out) >= 4
-    return b"".join(out)
-
-
 @pytest.mark.parametrize("deal_from_seed", [False, True])
 def test_replay_load_pool_allocation_failures(emu, played, deal_from_seed):
     """For every allocation and every synchronise the call makes: the call fails, nothing is freed twice, the destination still

@@ -1,7 +1,6 @@
 """The sample store (mortal_amd/csrc/mj_samples.hip behind mj_samples_*; SampleStore, GameplayLoader.store_pool / store_harvest, the
 runners' sample_store), run on the host emulation of the device code.  The cases and their yardsticks live in
 tests/sample_store_cases.py, shared with the `-m gpu` leg; the allocation and synchronise failures at the end are the emulator's own."""
-import ctypes as C
 import gc
 import os
 import shutil
@@ -14,6 +13,7 @@ HOST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host")
 if HOST not in sys.path:
     sys.path.insert(0, HOST)
 
+from emu_alloc import stats as _stats  # noqa: E402
 import pool_gameplay_cases as G  # noqa: E402
 import sample_store_cases as SC  # noqa: E402
 
@@ -83,12 +83,6 @@ def test_self_play_runner_sample_store(oracle, emu):
 
 
 # ---- allocation and synchronise failures (as tests/test_emu_pool_gameplay.py sweeps mj_replay_load_pool)
-def _stats(L):
-    out = (C.c_uint64 * 6)()
-    L.mj_emu_alloc_stats(out)
-    return dict(live=(out[0], out[1], out[2]), bad_frees=out[3], alloc=out[4], sync=out[5])
-
-
 @pytest.mark.parametrize("version", [3, 4])
 def test_allocation_and_synchronise_failures(emu, version):
     """For every allocation and every synchronise of mj_samples_create, mj_samples_append and the store's first mj_samples_encode

@@ -6,10 +6,11 @@ Per pool size (default 256 and 1,024 tables): plays that many hanchan (obs v3, t
 completion, then runs both routes over the same finished pool, interleaved in this one process: --repeats pairs, the first pair
 is the warm-up (reported, not in the medians).  Host clock around each route; both end in device synchronises (the copy of the
 sample metadata to the host).  The new route is split by timing its calls of log_grp and replay_load_pool (pack + grp); the rest
-is the replay loop, the sample ordering and the slicing, which both routes share.  The old route is split at its call of
-replay_load: what comes before is the host codec (log copy, decode, JSON text, json.loads, Grp.load_events, encode_events).
-One seat per table is tracked by default (--seats 1): every obs of the range is materialised on the device, 128,570 B per obs-v3
-sample, and four seats of 1,024 tables do not fit beside their own reordered copy.
+is what both routes share: the replay loop into a sample store of the call's own, and its Gameplays, encoded once in the
+reference's order (GameplayLoader._load).  The old route is split at its call of replay_load: what comes before is the host codec
+(log copy, decode, JSON text, json.loads, Grp.load_events, encode_events).  One seat per table is tracked by default (--seats 1):
+every obs of the range is materialised on the device, 128,570 B per obs-v3 sample, and this tool holds the results of both
+routes at once to compare them -- 30 GB each for one seat of 1,024 tables.
 
 The two routes must give the same samples (checked on the warm-up pair).  No ratio is gated: the file records what came out.
 Writes profiles/pool_gameplay_bench.json.  Needs a GPU; there is no fallback.

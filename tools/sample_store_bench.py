@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measures the sample store (mortal_amd/samples.py: decisions kept as 2 KB records, encoded when a batch draws them) against
-`GameplayLoader.load_pool`, which materialises every obs of the range on the device -- the route the store does not change, so it
-stands for the tree before the store existed.
+`GameplayLoader.load_pool`, which materialises every obs of the range on the device: the same replay into a store of its own,
+then every sample encoded at once.
 
 One pool of --tables finished hanchan (obs v3 play, the device's greedy policy, event log on; the log does not depend on the obs
 version), --seats tracked seats per table.  Per obs version (default 3 and 4), in this one process:
