@@ -123,11 +123,10 @@ std::vector<float> build_rbf(int n_max, int cap, int intervals) {
     return out;
 }
 
-// pad: PoolKnobs::enc_lds_pad
-size_t enc_lds_bytes(int version, size_t pad) {
+size_t enc_lds_bytes(int version) {
     int C = enc_rows_written(version);
     int tile_rows = ((C + ENC_PASSES - 1) / ENC_PASSES + 1) & ~1;
-    return (size_t)tile_rows * 34 * 4 + ((sizeof(TableOne) + 15) & ~(size_t)15) + sizeof(EncDerived) + pad;
+    return (size_t)tile_rows * 34 * 4 + ((sizeof(TableOne) + 15) & ~(size_t)15) + sizeof(EncDerived);
 }
 
 // The library's environment switches (diagnostics and tests; tools/README.md), read once per pool by mj_pool_create.  The SP
@@ -139,13 +138,6 @@ struct PoolKnobs {
     bool sp_wide_serial = false;    // MJ_SP_WIDE_SERIAL: the schedule's three launches one after the other (always in the emulator)
     bool sp_wide_all_rows = false;  // MJ_SP_WIDE_ALL_ROWS (tests, serial only): the wide kernel alone first, it takes every row
     bool sp_prof = false;           // MJ_SP_PROF: mj_k_sp's phase / pass timers, printed by mj_counters
-    // MJ_ENC_LDS_PAD (measurement only): extra dynamic LDS per encoder workgroup = fewer resident workgroups per CU (round 6: the
-    // encoder is FASTER with four than with five or six -- concurrent write streams, not occupancy, limit it)
-    size_t enc_lds_pad = 0;
-    int enc_grid = 256 * ENC_WPS;   // MJ_ENC_GRID: the persistent encoder's grid (ENC_PERSIST builds; default ENC_WPS per CU)
-#ifdef SP_ROWDUMP
-    std::string sp_rowdump;         // MJ_SP_ROWDUMP: file the per-row cost records of every SP launch are appended to
-#endif
 };
 
 PoolKnobs read_knobs() {
@@ -164,11 +156,6 @@ PoolKnobs read_knobs() {
 #endif
     K.sp_wide_all_rows = getenv("MJ_SP_WIDE_ALL_ROWS") != nullptr;
     K.sp_prof = getenv("MJ_SP_PROF") != nullptr;
-    if (auto v = num("MJ_ENC_LDS_PAD")) K.enc_lds_pad = (size_t)*v;
-    if (auto v = num("MJ_ENC_GRID")) K.enc_grid = std::max(1, *v);
-#ifdef SP_ROWDUMP
-    if (const char* v = getenv("MJ_SP_ROWDUMP")) K.sp_rowdump = v;
-#endif
     return K;
 }
 
@@ -448,7 +435,7 @@ MjPool* mj_pool_create(int n_tables, int version, int deal_algo, int max_rows) {
     for (int v = 1; v <= 4; v++) {
         const void* fn = v == 1 ? (const void*)mj_k_encode<1> : v == 2 ? (const void*)mj_k_encode<2>
                        : v == 3 ? (const void*)mj_k_encode<3> : (const void*)mj_k_encode<4>;
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds_bytes(v, P->knobs.enc_lds_pad));
+        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds_bytes(v));
     }
     return P.release();
 }
@@ -811,51 +798,12 @@ static int sp_setup(MjPool* P, const EncSrc& src, float* obs, hipStream_t s) {
     return 0;
 }
 
-#ifdef SP_ROWDUMP
-// (debug) MJ_SP_ROWDUMP: the per-row cost records of every launch appended to that file, one synchronous copy per launch
-// (`dump` belongs to sp_launch: whatever happens in between, the records are freed when the launch returns)
-static int rowdump_begin(MjPool* P, SpParams& kp, DevBuf<uint32_t>& dump, hipStream_t s) {
-    if (dump.alloc((size_t)kp.n_rows * 12)) return -1;
-    kp.rowdump = dump.get();
-    HIP_OK(hipMemsetAsync(kp.rowdump, 0, (size_t)kp.n_rows * 48, s));
-    HIP_OK(hipMemsetAsync(P->sp.err.get() + SP_ERR_DUMP_T0, 0xFF, 8, s));
-    HIP_OK(hipMemsetAsync(P->sp.err.get() + SP_ERR_DUMP_NARROW, 0, 24, s));
-    return 0;
-}
-static int rowdump_end(MjPool* P, const SpParams& kp, DevBuf<uint32_t>& dump, hipStream_t s) {
-    const int n = kp.n_rows;
-    std::vector<uint32_t> h((size_t)n * 12);
-    int q[SP_Q_WORDS];
-    HIP_OK(hipMemcpyAsync(h.data(), kp.rowdump, (size_t)n * 48, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(q, P->sp.queue.get(), sizeof(q), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    dump.reset();
-    if (std::unique_ptr<FILE, int (*)(FILE*)> f{fopen(P->knobs.sp_rowdump.c_str(), "ab"), fclose}) {
-        uint32_t hdr[12] = {0xFFFFFFFFu, (uint32_t)n};
-        unsigned long long tt[4];
-        HIP_OK(hipMemcpy(tt, P->sp.err.get() + SP_ERR_DUMP_T0, sizeof tt, hipMemcpyDeviceToHost));
-        for (int k = 0; k < 4; k++) hdr[2 + k] = (uint32_t)tt[k];  // first workgroup in, last narrow / wide out of the row loop, end of the tail
-        fwrite(hdr, 4, 12, f.get());
-        uint32_t cc[12];
-        for (int k = 0; k < 12; k++) cc[k] = k < 8 ? (uint32_t)q[1 + k] : 0u;
-        fwrite(cc, 4, 12, f.get());
-        for (int i = 0; i < n; i++)
-            if (h[(size_t)i * 12 + 7]) fwrite(&h[(size_t)i * 12], 4, 12, f.get());
-    }
-    return 0;
-}
-#endif
-
 // One SP launch over the n rows just encoded: the row order, then mj_k_sp alone or the small-pool schedule
 static int sp_launch(MjPool* P, const EncSrc& src, float* obs, int n, hipStream_t s) {
     SpResources& R = P->sp;
     HIP_OK(hipMemsetAsync(R.queue.get(), 0, SP_Q_WORDS * sizeof(int), s));
     SpParams kp = sp_params(src, R, obs, n);
     kp.prof = P->knobs.sp_prof ? R.err.get() : nullptr;
-#ifdef SP_ROWDUMP
-    DevBuf<uint32_t> dump;
-    if (!P->knobs.sp_rowdump.empty() && rowdump_begin(P, kp, dump, s)) return -1;
-#endif
     const int grid = std::min(n, R.grid);
     // The schedule needs mj_k_sp_wide and mj_k_sp_promo side by side.  Where they do not overlap -- more streams in the process than the
     // runtime has hardware queues, so that the promo kernel queues up BEHIND the spinning wide kernel -- the wide workgroups give up
@@ -868,7 +816,7 @@ static int sp_launch(MjPool* P, const EncSrc& src, float* obs, int n, hipStream_
     }
     const bool hybrid = R.spare > 0 && !P->sp_wide_off && (P->sp_wide_mode > 0 || (P->sp_wide_mode < 0 && n <= P->sp_wide_max_rows));
     kp.promo_cap = hybrid ? R.spare : 0;
-    // Defaults measured on MI355X (tools/r06_sweep.sh): up to ~12 k rows 64 wide workgroups (a quarter of the CUs),
+    // Defaults measured on MI355X: up to ~12 k rows 64 wide workgroups (a quarter of the CUs),
     // rows parked at >= 1,200 level-1 states (or >= 400 level-2 states, before that level is expanded); up to ~20 k rows 32 wide
     // workgroups and 1,600 level-1 states; beyond that a launch keeps all CUs for mj_k_sp (sp_wide_max_rows).  The root level is never
     // parked (nothing is known yet), level 0 is not expanded.
@@ -908,9 +856,6 @@ static int sp_launch(MjPool* P, const EncSrc& src, float* obs, int n, hipStream_
         hipLaunchKernelGGL(mj_k_sp_wide, dim3(wgrid), dim3(SP_WIDE_THREADS), 0, s, kp);
         HIP_OK(hipMemcpyAsync(R.gaveup_host.get(), R.err.get() + SP_ERR_WIDE_GAVEUP, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     }
-#ifdef SP_ROWDUMP
-    if (kp.rowdump && rowdump_end(P, kp, dump, s)) return -1;
-#endif
     return 0;
 }
 
@@ -933,18 +878,13 @@ static int encode_launch(MjPool* C, int agent, const EncSrc& src, int n, float* 
     ep.rbf_12 = g_tables.rbf_12;
     ep.rbf_23 = g_tables.rbf_23;
     ep.err_flag = C->enc_flag.get();
-    size_t lds = enc_lds_bytes(ep.version, C->knobs.enc_lds_pad);
+    size_t lds = enc_lds_bytes(ep.version);
     if (C->timing && C->enc_timer.begin(s)) return -1;
-#if ENC_PERSIST
-    const int egrid = std::min(n, C->knobs.enc_grid);
-#else
-    const int egrid = n;
-#endif
     switch (ep.version) {
-        case 1: hipLaunchKernelGGL(mj_k_encode<1>, dim3(egrid), dim3(ENC_THREADS), lds, s, ep); break;
-        case 2: hipLaunchKernelGGL(mj_k_encode<2>, dim3(egrid), dim3(ENC_THREADS), lds, s, ep); break;
-        case 3: hipLaunchKernelGGL(mj_k_encode<3>, dim3(egrid), dim3(ENC_THREADS), lds, s, ep); break;
-        default: hipLaunchKernelGGL(mj_k_encode<4>, dim3(egrid), dim3(ENC_THREADS), lds, s, ep); break;
+        case 1: hipLaunchKernelGGL(mj_k_encode<1>, dim3(n), dim3(ENC_THREADS), lds, s, ep); break;
+        case 2: hipLaunchKernelGGL(mj_k_encode<2>, dim3(n), dim3(ENC_THREADS), lds, s, ep); break;
+        case 3: hipLaunchKernelGGL(mj_k_encode<3>, dim3(n), dim3(ENC_THREADS), lds, s, ep); break;
+        default: hipLaunchKernelGGL(mj_k_encode<4>, dim3(n), dim3(ENC_THREADS), lds, s, ep); break;
     }
     if (C->timing && C->enc_timer.end(s)) return -1;
     HIP_OK(hipGetLastError());

@@ -42,38 +42,15 @@ struct EncParams {
 #define ENC_THREADS 256
 // obs v4: rows 889 .. 1011 (the SP block) belong to mj_k_sp; row 889 is only 8-byte aligned, so the split is at row 890 (889 leaves here as zeros)
 constexpr int enc_rows_written(int version) { return version == 1 ? 938 : version == 2 ? 942 : version == 3 ? 934 : 890; }
-#ifndef ENC_PASSES
-#define ENC_PASSES 8   // output passes per decision row = LDS tile of C / 8 rows.  With the op list a pass is {zero, apply, stream}: more,
-                       // smaller tiles only cost barriers and buy resident workgroups (5 per CU at 8 passes).  Measured (round 4, one box,
-                       // mj_k_encode<3> / <4> per launch): rounds 1-3 code 1.873 / 1.888 ms -> op list with 4 passes 1.756 / 1.790 ->
-                       // 6 passes 1.571 / 1.776 -> 8 passes 1.573 / 1.709 ms (0.67 of the HBM spec peak for both versions)
-#endif
-#ifndef ENC_OPS
-#define ENC_OPS 1024   // cell assignments of one decision row: < 1,000 by construction (96 displayed discards x <= 7 cells, 64 meld tiles,
-                       // 14 hand tiles x 4, the 34-wide rows); measured maximum 395 (enc_ops_high_water); an overflow is reported, never silent
-#endif
+// What these three are set to was measured (round 4 and round 6); the alternatives and what limits the kernel: DESIGN.md section 4,
+// profiles/r06_encode_limiter.md.
+#define ENC_PASSES 8   // output passes per decision row = LDS tile of C / 8 rows.  mj_k_encode<3> / <4> per launch with 4 / 6 / 8 passes:
+                       // 1.756 / 1.790 -> 1.571 / 1.776 -> 1.573 / 1.709 ms (smaller tiles buy resident workgroups and cost only barriers)
+#define ENC_OPS 1024   // cell assignments of one decision row: < 1,000 by construction, measured maximum 395 (enc_ops_high_water); an
+                       // overflow is reported, never silent
 #define ENC_FILLS 512  // whole-row fills of one decision row: <= 4 flag rows per displayed discard + ~100 scalar rows (measured maximum 145)
-#ifndef ENC_WPS
-#define ENC_WPS 4   // resident wavefronts per SIMD = workgroups per CU.  What limits this kernel (round 6; DESIGN.md section 4, profiles/r06_encode_limiter.md):
-                    //  * occupancy is NOT it: with extra LDS per workgroup (MJ_ENC_LDS_PAD) 2 / 3 / 4 / 5 / 6 workgroups per CU run mj_k_encode<3> in
-                    //    2.62 / 1.87 / 1.58 / 1.70 / 1.71 ms.  Four is what the 101 VGPRs of the has_yaku probe's callee (agari_search) leave; a build
-                    //    with that probe inlined (80 VGPRs, 88 B of scratch instead of 101 / 224) admits five or six -- and is slower for it;
-                    //  * a workgroup's 22.4 us: record load 1.2, op-list build 12.7 (per-seat scalars 3.9, kawa decode 3.1, record 4.5 on the slowest
-                    //    wavefront), zero + apply 3.9, stream-out 4.6 -- 1,024 resident workgroups x 127 KB / 22.4 us = 5.8 TB/s;
-                    //  * a restructured build phase (kawa decode by bit masks, one list reservation per task lane, single-lane tasks spread over
-                    //    the wavefronts, tiles zeroed behind their read: tools/experiments/r06_mj_encode_restructured.hip.txt, bit-exact) brings
-                    //    the workgroup to 21.7 us and the KERNEL from 1.58 to 1.65 ms; persistent workgroups (ENC_PERSIST) 1.79 ms;
-                    //  * PMC: wavefronts wait 61 % of their life, VALU active 12 %, LDS bank conflicts 0.6 %, the L2's write requests to the fabric
-                    //    stall 2 % of the channel cycles, the CUs' L1 61 % of the time on pending stores.
-                    // => the limit is how the memory system takes ~1,000 independent 15 KB write streams (5.3-5.5 TB/s on every box, a plain fill:
-                    //    5.0-6.2), not anything the kernel's own instruction stream or occupancy can buy back.
-#endif
-#ifndef ENC_PERSIST
-#define ENC_PERSIST 0   // 1: persistent workgroups (ENC_WPS per CU) looping over the rows.  Measured slower (round 6): 1.79 vs 1.58 ms
-#endif
-#ifndef ENC_NT
-#define ENC_NT 1   // non-temporal stores for the plane stack: it is written once and never re-read by this kernel
-#endif
+#define ENC_WPS 4      // resident wavefronts per SIMD = workgroups per CU: 2 / 3 / 4 / 5 / 6 per CU run mj_k_encode<3> in 2.62 / 1.87 / 1.58 /
+                       // 1.70 / 1.71 ms.  Concurrent write streams limit the kernel, not occupancy; persistent workgroups were slower (1.79 ms)
 
 #ifdef MJ_EMU
 // host emulation only: the largest op / fill lists seen (MJ_ENC_STATS=1 prints them at exit) — how ENC_OPS / ENC_FILLS were sized
@@ -191,12 +168,7 @@ __global__ __launch_bounds__(ENC_THREADS, ENC_WPS) void mj_k_encode(EncParams P)
     EncDerived* D = reinterpret_cast<EncDerived*>(reinterpret_cast<char*>(st) + ((sizeof(TableOne) + 15) & ~(size_t)15));
 
     const int tid = threadIdx.x;
-#if ENC_PERSIST
-    for (int row = blockIdx.x; row < P.n_rows; row += gridDim.x) {
-#else
     const int row = blockIdx.x;
-    {
-#endif
     const uint32_t desc = P.rows[row];
     const int table = ROW_TABLE(desc), p = ROW_SEAT(desc);
     const bool at_kan_select = ROW_KAN(desc);
@@ -726,16 +698,11 @@ __global__ __launch_bounds__(ENC_THREADS, ENC_WPS) void mj_k_encode(EncParams P)
                 if (fb >= 0.f) v.y = fb;
                 if (fc >= 0.f) v.z = fc;
                 if (fd >= 0.f) v.w = fd;
-#if ENC_NT
                 __builtin_nontemporal_store(v, d4 + i);
-#else
-                d4[i] = v;
-#endif
             }
         }
         __syncthreads();
     }
-    }  // (the row loop)
 }
 
 // ================================================================ invisible ("oracle") observation, board.rs:679-782

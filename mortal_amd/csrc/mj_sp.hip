@@ -36,27 +36,15 @@
 
 // (c_sp_tab, the table-id shanten block set once by mj_tables_upload, is declared in mj_rules.h: the step kernel uses it too)
 
-#ifndef SP_THREADS
-#define SP_THREADS 256          // threads per workgroup = per decision row in flight.  Measured in round 3 (-DSP_THREADS=64: one row per
-                                // wavefront, 16 single-wavefront workgroups per CU): the summed wavefront time drops by 14 % (nothing waits
-                                // at workgroup barriers), but the heaviest rows (~6 k states) then take ~23 ms on their single wavefront
-                                // and the launch lasts as long as they do: 39.5 vs 22.5 ms.  Four wavefronts per row it stays.
-#endif
+#define SP_THREADS 256          // threads per workgroup = per decision row in flight.  One wavefront per row (64 threads, round 3) was measured
+                                // at 39.5 vs 22.5 ms per launch: the heaviest rows (~6 k states) then last ~23 ms on their single wavefront
 #define SP_CAP 16384           // hash slots per workgroup (max observed states per decision ~6k)
 #define SP_T 17                // MAX_TSUMOS_LEFT (sp/mod.rs:40)
 #define SP_MAX_CAND 14
-#ifndef SP_NS
 #define SP_NS 16               // states per expansion chunk (one chunk per wavefront)
-#endif
-#ifndef SP_SORT_MIN
 #define SP_SORT_MIN 8            // levels up to this size are evaluated in list order (no cost sort)
-#endif
-#ifndef SP_ITEM_CAP
 #define SP_ITEM_CAP 64         // draw items (state, required tile) per sub-batch of a chunk: one lane each
-#endif
-#ifndef SP_WPS
 #define SP_WPS 4               // resident wavefronts per SIMD the kernel is compiled for (register budget 512 / SP_WPS per lane)
-#endif
 #define SP_WGS (4 * SP_WPS * 64 / SP_THREADS)  // resident workgroups per CU
 
 #ifndef SP_SET_BUCKETS
@@ -71,9 +59,7 @@
 #define SP_NODES (SP_CAP + SP_SET_SLOTS)
 #define SP_ZERO_SLOT SP_NODES    // one node past the states' own: all zero, never written (the child of every draw entry of a dead tenpai level, sp_expand_dead_chunk)
 static_assert((SP_SET_BUCKETS & (SP_SET_BUCKETS - 1)) == 0 && SP_SET_BUCKETS >= 1 && SP_ZERO_SLOT < (1 << 15), "slots are 15-bit fields");
-#ifndef SP_TAIL_BATCH
 #define SP_TAIL_BATCH 4         // rows per pop in the tail of the queue (rows without a state graph, one row per wavefront)
-#endif
 #define SP_Q_TAIL 32            // index of the tail's head word in SpParams::queue
 // Small pools (round 6): a row whose state graph turns out large is PROMOTED by its 256-thread workgroup to a wide (SP_WIDE_THREADS)
 // workgroup of mj_k_sp_wide, which runs beside mj_k_sp on another stream (see "promotion" at mj_k_sp).  Queue words, one 128-byte line each:
@@ -82,13 +68,9 @@ static_assert((SP_SET_BUCKETS & (SP_SET_BUCKETS - 1)) == 0 && SP_SET_BUCKETS >= 
 #define SP_Q_PROMO_ALLOC(p) (128 + 64 * (p))  // promotions so far = the next free entry / spare work area of queue p
 #define SP_Q_PROMO_HEAD(p) (160 + 64 * (p))   // next entry of queue p a wide workgroup takes; + 1: the same for the sweep launch
 #define SP_Q_PROMO_ENT 256      // entries [queue][SP_PROMO_CAP / 2]: work area + 1 (published after an agent-scope release), -1 = taken
-#ifndef SP_PROMO_CAP
 #define SP_PROMO_CAP 512        // promotions per launch (= spare work areas), half of them per queue
-#endif
 #define SP_Q_WORDS (SP_Q_PROMO_ENT + SP_PROMO_CAP)
-#ifndef SP_WIDE_THREADS
 #define SP_WIDE_THREADS 1024
-#endif
 #define SP_POOL (SP_CAP * 32)   // child-list pool entries per workgroup
 #define SP_ITEMS (SP_CAP * 4)   // level-0 scoring items per workgroup
 #define SP_L0_MAX 17            // winning draw entries per tenpai state (13 waits + 3 aka variants)
@@ -181,7 +163,7 @@ struct SpParams {
     const uint32_t* order;     // [n_rows] queue position -> row index, heaviest cost class first (mj_k_order_classify / _scatter)
     unsigned long long* prof;  // NULL or [24] phase timers / counters (MJ_SP_PROF; mj_counters prints them)
     unsigned long long* err;   // [SP_ERR_WORDS] counter words (SpErrWord below)
-    uint32_t* rowdump;         // (builds with -DSP_ROWDUMP only: tools/build_variant.sh dump -DSP_ROWDUMP) NULL, or [n_rows][12] per-row records of the rows with a state graph (MJ_SP_ROWDUMP: cost-model data for the row order)
+    void* unused_;             // (never read: keeps the offsets of the fields below)
     // promotion of large rows to mj_k_sp_wide (small pools; see "promotion" at mj_k_sp)
     int promo_cap;             // spare work areas = promotions allowed in this launch (0: off); work[] holds grid + promo_cap areas
     int promo_min[4];          // [level]: park the row when the level about to be expanded has at least this many states
@@ -215,10 +197,7 @@ enum SpErrWord {
     SP_ERR_WIDE_GAVEUP = 25,  // wide workgroups that gave up waiting (the two kernels did not overlap)
     SP_ERR_PROMOTED = 26,     // rows parked and finished by mj_k_sp_wide
     SP_ERR_SWEPT = 27,        // rows the sweep launch had to take
-    SP_ERR_DUMP_T0 = 28,      // (-DSP_ROWDUMP) first workgroup start of the graph-row loops,
-    SP_ERR_DUMP_NARROW = 29,  //   last narrow / ...
-    SP_ERR_DUMP_WIDE = 30,    //   ... wide workgroup out of them,
-    SP_ERR_DUMP_TAIL = 31,    //   end of the queue's tail
+    // (28 .. 31: unused)
     SP_ERR_DEAD_LEAF = 32,    // rows with as many draws left as their shanten number (the last draw only reaches tenpai): level 1 expanded by
                               // sp_expand_dead_chunk, level 0 neither built nor evaluated
     SP_ERR_WORDS = 33
@@ -452,51 +431,28 @@ MJD bool sp_tag_free(u64 t, u32 ep) { return (u32)((t >> 42) & SP_EPOCH_MAX) != 
 //    top of the kernel and spilled them (50 stores up front, reloads inside the probe passes).  An opaque copy of the lane id per
 //    row / per chunk stops the hoisting: the constants are recomputed (1-2 VALU) where they are used.
 // Measured: 20.93 -> 19.76 ms (inline) -> 18.45 ms (+ opaque lane id) on one box; 19.99 -> 18.17 ms on another.
-#ifndef SP_OPAQUE_TID
-#define SP_OPAQUE_TID 2  // 0: off, 1: per expansion chunk, 2: + per row of the queue
-#endif
+// SP_OPQ(level, v): level 1 = per expansion chunk, 2 = per row of the queue.  (An opaque copy of the uniform pointers -- the table
+// directory, the work area -- was measured neutral to slightly slower, 18.82 vs 18.45 ms, and is not made.)
 #if defined(MJ_EMU)
 #define SP_OPQ(level, v) (v)
 #else
 __device__ __forceinline__ int sp_opaque_v(int v) { asm volatile("" : "+v"(v)); return v; }
-#define SP_OPQ(level, v) ((SP_OPAQUE_TID) >= (level) ? sp_opaque_v(v) : (v))
-#endif
-// ... and of a uniform pointer (the table directory in constant memory, the work area).  Measured neutral to slightly slower
-// (18.82 vs 18.45 ms): off by default.
-#if defined(MJ_EMU) || !defined(SP_OPAQUE_PTR)
-#define SP_OPQ_PTR(level, p) (p)
-#else
-template <typename Tp> __device__ __forceinline__ Tp* sp_opaque_s(Tp* p) { asm volatile("" : "+s"(p)); return p; }
-#define SP_OPQ_PTR(level, p) ((SP_OPAQUE_PTR) >= (level) ? sp_opaque_s(p) : (p))
-#endif
-#ifndef SP_ATTR_EXPAND
-#define SP_ATTR_EXPAND __forceinline__
-#endif
-#ifndef SP_ATTR_L0P
-#define SP_ATTR_L0P __noinline__
-#endif
-#ifndef SP_ATTR_L0S
-#define SP_ATTR_L0S __noinline__
-#endif
-#ifndef SP_ATTR_EVAL
-#define SP_ATTR_EVAL __noinline__
-#endif
-#ifndef SP_ATTR_EVAL0
-#define SP_ATTR_EVAL0 __noinline__
+#define SP_OPQ(level, v) sp_opaque_v(v)
 #endif
 
 #ifdef MJ_EMU
 // claims lost since the library was loaded (only an emulator whose atomics yield can lose one), to the same id / to another id:
 // [0..1] every claim (sp_claim_tag), [2..3] those of them on a way of the LDS set (sp_set_find_or_claim); the rest is the HBM table
 inline unsigned long long g_sp_emu_lost[4];
+inline void sp_emu_lost(int k) { g_sp_emu_lost[k]++; }
+#else
+MJD void sp_emu_lost(int) {}
 #endif
 template <class TagP>
 MJD u64 sp_claim_tag(TagP tagp, u64 h, u64 seen) {  // claim a slot seen empty (holding `seen`): atomicCAS(tag, seen, h) (relaxed, agent scope)
     u64 expected = seen;                            // -> 0 = claimed, else the tag found there (of this row: only this workgroup writes its table)
     __hip_atomic_compare_exchange_strong(tagp, &expected, h, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef MJ_EMU
-    if (expected != seen) g_sp_emu_lost[expected != h ? 1 : 0]++;
-#endif
+    if (expected != seen) sp_emu_lost(expected != h ? 1 : 0);
     return expected == seen ? 0ull : expected;
 }
 // hash-set insert of the state `base` + draw `tile` - discard `dt` (either may be -1) with id `dk`: returns the slot or -1 on
@@ -549,6 +505,11 @@ inline void sp_emu_check_unique(WP W, SpCtx* X) {
     if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) X->overflow = 1;
 }
 inline unsigned long long g_sp_emu_placed[2];  // states placed in the LDS set / in the HBM table (tests: a small set must send states both ways)
+inline void sp_emu_placed(int k) { g_sp_emu_placed[k]++; }
+#else
+template <class WP> MJD void sp_emu_check_hit(WP, SpCtx*, u32, u64, const SpState&) {}
+template <class WP> MJD void sp_emu_check_unique(WP, SpCtx*) {}
+MJD void sp_emu_placed(int) {}
 #endif
 // The LDS part of the hash set (mj_k_sp): SP_SET_BUCKETS buckets of two ways, each way a tag as in SpWork::tag (a tag of another epoch
 // is a free way; nothing is cleared between rows).  A state has two buckets; both are read (one ds_read_b128 each, issued together)
@@ -570,9 +531,7 @@ __device__ __forceinline__ int sp_set_find_or_claim(u64* set, u32 h, u64 tag, u3
         if (!sp_tag_free(w[i], ep)) continue;  // another state of this row: for good
         const u32 slot = 2 * b[i >> 1] + (i & 1);
         const u64 old = sp_claim_tag(&set[slot], tag, w[i]);
-#ifdef MJ_EMU
-        if (old != 0ull) g_sp_emu_lost[2 + (old != tag ? 1 : 0)]++;
-#endif
+        if (old != 0ull) sp_emu_lost(2 + (old != tag ? 1 : 0));
         if (old == 0ull) return (int)slot | (1 << 16);
         if (old == tag) return (int)slot;  // another lane has just placed this very state here
     }
@@ -590,10 +549,8 @@ __device__ __forceinline__ int sp_insert(WP W, SpCtx* X, u64 dk, const SpState& 
         const int r = sp_set_find_or_claim(set, h, tag, ep);
         if (r >= 0) {
             if (r >> 16) sp_new_state(W, X, (u32)(r & 0xFFFF), dk, sp_apply(base, tile, dt));
-#ifdef MJ_EMU
-            if (r >> 16) g_sp_emu_placed[0]++;
+            if (r >> 16) sp_emu_placed(0);
             else sp_emu_check_hit(W, X, (u32)r, dk, sp_apply(base, tile, dt));
-#endif
             return r & 0xFFFF;
         }
     }
@@ -603,15 +560,11 @@ __device__ __forceinline__ int sp_insert(WP W, SpCtx* X, u64 dk, const SpState& 
         if (sp_tag_free(old, ep)) old = sp_claim_tag(&W->tag[pos], tag, old);
         if (old == 0ull) {
             sp_new_state(W, X, HB + pos, dk, sp_apply(base, tile, dt));
-#ifdef MJ_EMU
-            g_sp_emu_placed[1]++;
-#endif
+            sp_emu_placed(1);
             return (int)(HB + pos);
         }
         if (old == tag) {
-#ifdef MJ_EMU
             sp_emu_check_hit(W, X, HB + pos, dk, sp_apply(base, tile, dt));
-#endif
             return (int)(HB + pos);
         }
         pos = (pos + 1) & (SP_CAP - 1);
@@ -772,7 +725,7 @@ __device__ __forceinline__ void sp_l0_score(SpWork* W, const SpScoreRow& R, u32 
 // The dense scoring pass of one wavefront: its share of the row's work items in ONE call (a call per item and lane saved and restored the
 // function's 18 callee-saved VGPRs every 64 items).  The item loop itself makes no call and touches no stack: the row's constants are
 // read once, an item's hand goes to the inlined agari code in registers (tests/test_sp_score_isa.py pins both).
-__device__ SP_ATTR_L0S void sp_l0_score_all(SpWork* W, const SpCtx* X, int n_items, int tid, int stride) {
+__device__ __noinline__ void sp_l0_score_all(SpWork* W, const SpCtx* X, int n_items, int tid, int stride) {
     const SpScoreRow R = sp_score_row(X);
     const SP_HBM u32* const items = ((SP_HBM SpWork*)W)->items;
     for (int i = tid; i < n_items; i += stride) sp_l0_score(W, R, items[i], i);
@@ -862,8 +815,8 @@ struct SpChunk {
                                             // item | kept discard << 6 | draw variant << 12 | last discard of the draw entry << 13
 };
 #define SP_NT 64  // co-operating threads of a chunk
-#define SP_SB (SP_NS > 16 ? 5 : 4)  // bits of the state index inside an item
-static_assert(SP_NS == 16 || SP_NS == 32, "n_tiles is read in 16-byte words; item entries hold the state in SP_SB bits");
+#define SP_SB 4  // bits of the state index inside an item
+static_assert(SP_NS == (1 << SP_SB) && SP_NS == 16, "n_tiles is read in 16-byte words; item entries hold the state in SP_SB bits");
 static_assert(SP_ITEM_CAP == SP_NT, "one lane per draw item: the layout pass is a wavefront scan");
 
 MJD SpState sp_chunk_state(const SpChunk* C, int s) {
@@ -952,11 +905,11 @@ __device__ __forceinline__ void sp_chunk_probe(SP_HBM SpWork* Wg, SpCtx* X, SpCh
 
 // Level 0: which draws win and one scoring work item per draw entry, in the reference's order (plain tile if a non-red
 // copy is left, then the red five); the state's header gets the entry counts, their number and the not_tsumo row.
-__device__ SP_ATTR_L0P void sp_l0_probe_chunk(SpWork* W, SpCtx* X, SpChunk* C, int first, int n) {
+__device__ __noinline__ void sp_l0_probe_chunk(SpWork* W, SpCtx* X, SpChunk* C, int first, int n) {
     SP_ASSUME_LDS(X);
     SP_ASSUME_LDS(C);
     SP_HBM SpWork* const Wg = (SP_HBM SpWork*)W;
-    const SpTabG TG = sp_tab_g(*SP_OPQ_PTR(1, &c_sp_tab));
+    const SpTabG TG = sp_tab_g(c_sp_tab);
     sp_chunk_probe(Wg, X, C, TG, first, n, 0);
     const int s = threadIdx.x & (SP_NT - 1);
     if (s < n) {
@@ -1001,11 +954,11 @@ __device__ SP_ATTR_L0P void sp_l0_probe_chunk(SpWork* W, SpCtx* X, SpChunk* C, i
 
 // Levels >= 1: required draws, shanten-keeping discards and the children of SP_NS states.
 template <bool LDS_SET>  // mj_k_sp: the first part of the hash set in LDS; the other two kernels: the child cache in front of the HBM table
-__device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, int first, int n, int L) {
+__device__ __forceinline__ void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, int first, int n, int L) {
     SP_ASSUME_LDS(X);
     SP_ASSUME_LDS(C);
-    SP_HBM SpWork* const Wg = (SP_HBM SpWork*)SP_OPQ_PTR(2, W);
-    const SpTabG TG = sp_tab_g(*SP_OPQ_PTR(1, &c_sp_tab));
+    SP_HBM SpWork* const Wg = (SP_HBM SpWork*)W;
+    const SpTabG TG = sp_tab_g(c_sp_tab);
     const int tid = SP_OPQ(1, (int)(threadIdx.x & (SP_NT - 1)));
     const int ld3 = X->len_div3;
     const u32 tag_ep = X->tag_epoch;
@@ -1218,21 +1171,17 @@ __device__ SP_ATTR_EXPAND void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C, 
 #ifdef MJ_EMU
             if (LDS_SET && known >= 0 && !fresh) sp_emu_check_hit(Wg, X, (u32)cs, E.dk, sp_apply(Sx, E.tile, E.dt));
             if (!LDS_SET && known >= 0 && Wg->tag[known] != tag) X->overflow = 1;  // a cache hit must name the slot that holds this very state
-            if (fresh) g_sp_emu_placed[0]++;
 #endif
+            if (fresh) sp_emu_placed(0);
             for (int probe = 0; cs < 0 && probe < SP_CAP; probe++) {
                 if (old == 0ull) {
                     fresh = true;
                     cs = (int)(HB + pos);
-#ifdef MJ_EMU
-                    g_sp_emu_placed[1]++;
-#endif
+                    sp_emu_placed(1);
                     break;
                 }
                 if (old == tag) {
-#ifdef MJ_EMU
                     sp_emu_check_hit(Wg, X, HB + pos, E.dk, sp_apply(Sx, E.tile, E.dt));
-#endif
                     cs = (int)(HB + pos);
                     break;
                 }
@@ -1329,7 +1278,7 @@ __device__ __noinline__ void sp_expand_dead_chunk(SpWork* W, SpCtx* X, SpChunk* 
     SP_ASSUME_LDS(X);
     SP_ASSUME_LDS(C);
     SP_HBM SpWork* const Wg = (SP_HBM SpWork*)W;
-    const SpTabG TG = sp_tab_g(*SP_OPQ_PTR(1, &c_sp_tab));
+    const SpTabG TG = sp_tab_g(c_sp_tab);
     const bool prof = X->prof != nullptr;
     const long long tq0 = prof ? wall_clock64() : 0;
     sp_chunk_probe(Wg, X, C, TG, first, n, 1);
@@ -1412,7 +1361,7 @@ __device__ static const u8 SP_EVW_STRIDE[SP_T + 1][4] = {
 // Per step up to SP_EV_ENT entries of every team: lane j parks A[j] = tsumo_prob[count][j] * not_tsumo[j], then every lane i adds
 // prob(i, j) and prob(i, j) * score for j = i .. T-1 (the score picked by riichi-ippatsu at j == i, haitei at j == T-1: calc.rs:510-527).
 template <int TN>
-__device__ SP_ATTR_EVAL0 void sp_eval_wave0(SpWork* W, SpCtx* X, float* WL, int first, int end, int stride, int lane_in_team, int off_,
+__device__ __noinline__ void sp_eval_wave0(SpWork* W, SpCtx* X, float* WL, int first, int end, int stride, int lane_in_team, int off_,
                                            int team_in_wave, bool team_on) {
     SP_ASSUME_LDS(X);
     SP_ASSUME_LDS(WL);
@@ -1568,7 +1517,7 @@ __device__ SP_ATTR_EVAL0 void sp_eval_wave0(SpWork* W, SpCtx* X, float* WL, int 
 // the next states' headers) are issued before the accumulate and consumed after it.  The f32 operation order per lane is the
 // reference's: entries in list order, turns ascending.
 template <int TN, int LK>
-__device__ SP_ATTR_EVAL void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int first, int end, int stride, int lane_in_team, int off_,
+__device__ __noinline__ void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int first, int end, int stride, int lane_in_team, int off_,
                                           int team_in_wave, bool team_on) {
     static_assert(LK >= 1, "level 0 has no children: sp_eval_wave0");
     SP_ASSUME_LDS(X);
@@ -2315,9 +2264,7 @@ struct SpHandoff {
     int row, next_lv;
 };
 static_assert(sizeof(SpHandoff) <= SP_HANDOFF_WORDS * 4 && sizeof(SpHandoff) % 4 == 0, "SpWork::handoff holds an SpHandoff");
-#ifndef SP_WIDE_TIMEOUT
 #define SP_WIDE_TIMEOUT 5000000ll  // wall_clock64 ticks (100 MHz): 50 ms (a legitimate wait ends with mj_k_sp_promo's last row: milliseconds)
-#endif
 // The hand-off's two fences (MI355X_MICROARCH.md, inter-workgroup visibility: per-XCD L2s are not coherent with each other, a CU's L1 is never
 // refreshed by another CU's stores).  Producer: every wavefront drains its stores, workgroup barrier, ONE lane releases at agent scope
 // (buffer_wbl2 sc1) and drains again (the compiler may drop the wait behind the write-back), then the relaxed agent-scope flag store.
@@ -2334,11 +2281,6 @@ static_assert(sizeof(SpHandoff) <= SP_HANDOFF_WORDS * 4 && sizeof(SpHandoff) % 4
 #define SP_SPIN_PAUSE() ((void)0)
 #endif
 
-#ifdef SP_ROWDUMP
-#define SP_DUMP(P) ((P).rowdump != nullptr)
-#else
-#define SP_DUMP(P) false  // (the debug records cost the kernel five VGPR spills)
-#endif
 template <int NT>
 struct SpLds {
     union Teams {
@@ -2372,7 +2314,6 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
     unsigned own_epoch = tag_epoch;  // (mj_k_sp_wide: the epoch of its own area while it works in a promoted row's)
     bool main_done = false, drained = false;  // (mj_k_sp_wide, lane 0: the row queue is empty; the last look at the promotion queues)
 
-    const long long t_wg_in = SP_DUMP(P) ? wall_clock64() : 0;
     const long long t_wg0 = P.prof ? wall_clock64() : 0;  // MJ_SP_PROF: workgroup lifetime / queue + reset time (SP_ERR_WG_LIFE .. SP_ERR_T_RESET)
 #ifndef MJ_EMU
     const long long c_wg0 = P.prof ? clock64() : 0;       // the same lifetime in shader-clock cycles (s_memtime, SP_ERR_WG_CLOCK)
@@ -2561,7 +2502,6 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                                     H->row = row;
                                     H->next_lv = lv;
                                     W->epoch = tag_epoch;
-                                    if (SP_DUMP(P)) P.rowdump[(size_t)row * 12 + 8] = (uint32_t)t_0, P.rowdump[(size_t)row * 12 + 9] = (uint32_t)wall_clock64();
                                 }
                             }
                             // every wavefront's stores of this row (nodes, keys, lists, pools ...) are in L2 before lane 0 releases them
@@ -2598,9 +2538,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
             }
             t_2 = wall_clock64();
             t_3 = t_2;  // (a row without level 0)
-#ifdef MJ_EMU
             if (tid == 0 && !parked) sp_emu_check_unique(W, &X);  // (its verdict is read after the row's last barrier)
-#endif
             // evaluate bottom-up
             if (!parked)
             for (int lv = (cur_shanten >= 1 && T == cur_shanten) ? 1 : 0; lv <= cur_shanten; lv++) {  // (leaf_dead: no probe, no scoring, no sort, no sums)
@@ -2683,17 +2621,6 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                     for (int k = 0; k < 7; k++) s_stat[SP_ERR_PASS + k] += X.pt[k];
                 if (P.prof) s_stat[SP_ERR_T_L0_PROBE] += X.pt[7];
             }
-            if (SP_DUMP(P) && !parked) {  // (debug) queue position | wide << 31, shanten | T << 8 | n_cand << 16 | can_discard << 24, sum of the candidates' required kinds, states, edges, l0 items, ticks, level sizes
-                uint32_t* d = P.rowdump + (size_t)row * 12;
-                int nreq = 0;
-                for (int c = 0; c < n_cand; c++) nreq += X.cand_nreq[c];
-                d[0] = (uint32_t)(WIDE ? 0x40000000 | (promoted ? 0x20000000 : 0) : s_row); d[1] = (uint32_t)(cur_shanten | T << 8 | n_cand << 16 | (int)can_discard << 24); d[2] = (uint32_t)nreq;
-                d[3] = with_probs ? (uint32_t)X.n_list : 0u; d[4] = with_probs ? (uint32_t)X.n_pool : 0u; d[5] = with_probs ? (uint32_t)X.n_items : 0u;
-                d[6] = (uint32_t)(t_5 - t_0);
-                if (!promoted) d[8] = (uint32_t)t_0, d[9] = 0u;
-                d[10] = (uint32_t)t_0; d[11] = (uint32_t)t_5;
-                d[7] = 0x80000000u | (with_probs ? (uint32_t)min(X.lvl_end[1] - X.lvl_begin[1], 32767) | (uint32_t)min(X.lvl_end[2] - X.lvl_begin[2], 32767) << 15 : 0u);
-            }
         }
         if constexpr (WIDE) {
             if (!promoted) own_epoch = tag_epoch;
@@ -2727,10 +2654,6 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         s_stat[SP_ERR_T_RESET] += (unsigned long long)t_reset;
     }
     __syncthreads();  // (every thread leaves the row loop at the same pop)
-    if (SP_DUMP(P) && tid == 0) {  // (debug) first workgroup start / last end of the graph-row loops, both kernels
-        atomicMin(&P.err[SP_ERR_DUMP_T0], (unsigned long long)t_wg_in);
-        atomicMax(&P.err[WIDE ? SP_ERR_DUMP_WIDE : SP_ERR_DUMP_NARROW], (unsigned long long)wall_clock64());
-    }
     if (tid < SP_ERR_STATS && tid != SP_ERR_WG_LIFE_MAX && s_stat[tid]) atomicAdd(&P.err[tid], s_stat[tid]);  // the workgroup's statistics, once
     if (tid == SP_ERR_STATS && s_stat[tid]) atomicAdd(&P.err[SP_ERR_DEAD_LEAF], s_stat[tid]);
     // ---- the tail of the queue: every wavefront takes its own rows (set-up + encoder only, no workgroup barrier any more)
@@ -2759,7 +2682,6 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
             atomicAdd(&P.err[SP_ERR_T_SETUP], w_ticks);
             if (w_over) atomicAdd(&P.err[SP_ERR_OVERFLOW], w_over);
         }
-        if (SP_DUMP(P) && lane == 0) atomicMax(&P.err[SP_ERR_DUMP_TAIL], (unsigned long long)wall_clock64());  // (debug) end of the tail
     }
     }
 }

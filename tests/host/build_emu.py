@@ -6,7 +6,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-EXTRA = os.environ.get("EMU_EXTRA_FLAGS", "").split()  # e.g. -DSP_OPT=7: validate an experimental kernel variant on the host
+EXTRA = os.environ.get("EMU_EXTRA_FLAGS", "").split()  # e.g. -DSP_SET_BUCKETS=64: build a kernel variant for the host
 OUT = os.path.join(HERE, "_build", "libmortal_amd_emu" + ("_" + "".join(c for c in "".join(EXTRA) if c.isalnum()) if EXTRA else "") + ".so")
 CXX = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
 

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-REAL = os.environ.get("MORTAL_AMD_CFG0_REAL") == "1"  # tools/r06_cfg0_gpu.sh: the real libmortal_amd.so and the networks on cuda:0
+REAL = os.environ.get("MORTAL_AMD_CFG0_REAL") == "1"  # on an MI355X (profiles/r06_cfg0_real_library.log): the real libmortal_amd.so and the networks on cuda:0
 KEY = 0xD5DFAA4CEF265CD7
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")

@@ -37,7 +37,7 @@ def pmc_rows(d, name):
 
 def main():
     src, rnd = sys.argv[1], sys.argv[2]
-    tables = int(sys.argv[3]) if len(sys.argv) > 3 else 65536  # table count of the PMC passes (tools/r03_full.sh: the bench's own)
+    tables = int(sys.argv[3]) if len(sys.argv) > 3 else 65536  # table count of the PMC passes (default: the bench's own)
     prof = os.path.join(ROOT, "profiles")
     os.makedirs(prof, exist_ok=True)
     for v in (3, 4):
