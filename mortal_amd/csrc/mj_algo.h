@@ -78,6 +78,28 @@ MJD float sp_div_domain(float a, float b, float r1) {
     const float e1 = __builtin_fmaf(-b, q0, a);
     return __builtin_fmaf(e1, r1, q0);
 }
+// Two divisions by the same divisor at once: per component the three operations of sp_div_domain, bit for bit (gfx950 has them as
+// v_pk_mul_f32 / v_pk_fma_f32 on an aligned register pair: one packed fma issues in 4.4-4.6 cycles where two plain ones take 6.9-8.6,
+// profiles/r03_ubench_valu.jsonl, profiles/ubench_valu_pk.jsonl).  tests/host/div2_check.hip runs both components over the domain above.
+typedef float MjF2 __attribute__((vector_size(8)));
+MJD MjF2 mj_f2(float x) { return MjF2{x, x}; }
+MJD MjF2 mj_fma2(MjF2 a, MjF2 b, MjF2 c) {
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_elementwise_fma)
+#define MJ_HAS_ELEMENTWISE_FMA 1
+#endif
+#endif
+#ifdef MJ_HAS_ELEMENTWISE_FMA
+    return __builtin_elementwise_fma(a, b, c);
+#else
+    return MjF2{__builtin_fmaf(a[0], b[0], c[0]), __builtin_fmaf(a[1], b[1], c[1])};
+#endif
+}
+MJD MjF2 sp_div_domain2(MjF2 a, float b, float r1) {
+    const MjF2 q0 = a * mj_f2(r1);
+    const MjF2 e1 = mj_fma2(mj_f2(-b), q0, a);
+    return mj_fma2(e1, mj_f2(r1), q0);
+}
 
 
 enum : int { T_5M = 4, T_5P = 13, T_5S = 22, T_E = 27, T_S = 28, T_W = 29, T_N = 30, T_P = 31, T_F = 32, T_C = 33,

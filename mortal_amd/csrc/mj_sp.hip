@@ -433,11 +433,16 @@ MJD bool sp_tag_free(u64 t, u32 ep) { return (u32)((t >> 42) & SP_EPOCH_MAX) != 
 // Measured: 20.93 -> 19.76 ms (inline) -> 18.45 ms (+ opaque lane id) on one box; 19.99 -> 18.17 ms on another.
 // SP_OPQ(level, v): level 1 = per expansion chunk, 2 = per row of the queue.  (An opaque copy of the uniform pointers -- the table
 // directory, the work area -- was measured neutral to slightly slower, 18.82 vs 18.45 ms, and is not made.)
+// SP_OPQ_F(v): the same for a float.  sp_eval_wave0 passes one of its two sums through it per term: otherwise the compiler pairs the
+// two chains into one v_pk_add_f32 per term and assembles each (prob, prob x score) operand with two v_mov_b32.
 #if defined(MJ_EMU)
 #define SP_OPQ(level, v) (v)
+#define SP_OPQ_F(v) (v)
 #else
 __device__ __forceinline__ int sp_opaque_v(int v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ float sp_opaque_f(float v) { asm("" : "+v"(v)); return v; }
 #define SP_OPQ(level, v) sp_opaque_v(v)
+#define SP_OPQ_F(v) sp_opaque_f(v)
 #endif
 
 #ifdef MJ_EMU
@@ -1474,11 +1479,17 @@ __device__ __noinline__ void sp_eval_wave0(SpWork* W, SpCtx* X, float* WL, int f
 #pragma unroll
                             for (int jj = 0; jj < 4; jj++) a4[jj] = al[4 * g + jj];  // past T - 2: zero
                             const float so_ = s_own, sb_ = s_base;  // values, not the lambda's references (else: pointer selects + flat loads)
+                            // two terms at a time where no sum chains them: the divisions and the score products
+                            MjF2 p2[2], ps2[2];
+#pragma unroll
+                            for (int h = 0; h < 2; h++) {
+                                p2[h] = sp_div_domain2(MjF2{a4[2 * h], a4[2 * h + 1]}, my_m, my_r);
+                                ps2[h] = p2[h] * MjF2{(g == 0 && h == 0) ? so_ : sb_, sb_};  // the lane's own turn first (riichi-ippatsu), then the plain score
+                            }
 #pragma unroll
                             for (int jj = 0; jj < 4; jj++) {
-                                const float prob_ = sp_div_domain(a4[jj], my_m, my_r);
-                                acc_w += prob_;
-                                acc_e += prob_ * ((g == 0 && jj == 0) ? so_ : sb_);  // the lane's own turn first (riichi-ippatsu), then the plain score
+                                acc_w = SP_OPQ_F(acc_w + p2[jj >> 1][jj & 1]);
+                                acc_e += ps2[jj >> 1][jj & 1];
                             }
                         }
                     });
@@ -1511,11 +1522,17 @@ __device__ __noinline__ void sp_eval_wave0(SpWork* W, SpCtx* X, float* WL, int f
 // unrolled loop was its own basic block behind an exec-mask branch (three LDS reads, a wait, eight VALU, three SALU).
 // Here a STEP = {fold SP_EV_ENT children per team (selects, no branches), park every completed draw
 // entry's folded row in the team's LDS buffer, issue the loads of the next step, accumulate ALL parked entries of ALL teams
-// together}: one b128 LDS read per turn (the row {nx_t, nx_w, nx_e, A}: the numerator A[j] = tsumo_prob[count][j] *
-// not_tsumo[j] rides in the spare word of row j + 1), turns in groups of four behind one scalar branch, rows past T are zero
+// together}: one 16-byte row per turn, turns in groups of four behind one scalar branch, rows past T are zero
 // (+0.0 terms).  The loads of the next step (child values, next child-list entries,
 // the next states' headers) are issued before the accumulate and consumed after it.  The f32 operation order per lane is the
 // reference's: entries in list order, turns ascending.
+// The parked row of turn j + 1 serves the term j (A[j] = tsumo_prob[count][j] * not_tsumo[j], the division's numerator):
+//   level 1  : {nx_w, nx_e, A[j], A[j + 1]} -- a lane starts its pairs of terms at its own turn, odd or even, so every row carries
+//              the numerator pair that starts at it (the tenpai value is not parked: level 1 never reads it);
+//   levels 2+: {nx_w, nx_e, nx_t, A[j]} -- five values do not fit the 16 bytes, the numerator pair is put together in registers.
+// (nx_w, nx_e) and the numerator pair arrive in aligned register pairs: per term one v_pk_mul_f32 + one v_pk_add_f32 into
+// (acc_w, acc_e), per two terms the three packed instructions of sp_div_domain2, and no v_mov_b32 at level 1 (18 VALU instructions
+// per group of four terms where the compiler's own pairing of the scalar code took 30, ten of them moves: tests/test_sp_eval_isa.py).
 template <int TN, int LK>
 __device__ __noinline__ void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int first, int end, int stride, int lane_in_team, int off_,
                                           int team_in_wave, bool team_on) {
@@ -1576,7 +1593,8 @@ __device__ __noinline__ void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
 
     int c0 = 0;
     float my_m = m_raw != 0.f ? m_raw : 1.f, my_r = sp_rcp_refined(my_m);
-    float acc_t = 0.f, acc_w = 0.f, acc_e = 0.f;
+    float acc_t = 0.f;
+    MjF2 acc_we = {0.f, 0.f};  // (win, EV): one aligned register pair, one accumulator chain each
     // discard_slow (calc.rs:570-637) fold state of the draw entry in progress
     // The fold's order (calc.rs:600-615: larger (int)EV first, then the discard priority) as ONE integer: (int)EV << 9 | order key.
     // (int)EV is non-negative and below 2^19 (six-fold yakuman of the dealer: 288,000), the key is 9 bits wide; the initial
@@ -1611,10 +1629,16 @@ __device__ __noinline__ void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
                 const u32 cnt = SP_ENT_COUNT(e);  // 1..4 copies of the drawn tile
                 const float tpc = cnt <= 1 ? tp0 : cnt == 2 ? tp1 : cnt == 3 ? tp2 : tp3;
                 float* row = row0 + koff;
-                if constexpr (LK != 1) row[0] = nx_t;  // (level 1: stays the zero fill, nobody reads it)
-                row[1] = nx_w;
-                row[2] = nx_e;
-                row[7] = tpc * m_raw;  // A[ln], read with row ln + 1
+                const float a = tpc * m_raw;  // A[ln], read with row ln + 1
+                row[0] = nx_w;
+                row[1] = nx_e;
+                if constexpr (LK == 1) {
+                    row[3] = a;  // the second numerator of the pair that starts at turn ln - 1
+                    row[6] = a;  // the first one of the pair that starts here
+                } else {
+                    row[2] = nx_t;
+                    row[7] = a;
+                }
                 k++;
                 koff += rows * 4;
                 nx_t = nx_w = nx_e = -3.40282347e+38f;
@@ -1649,7 +1673,7 @@ __device__ __noinline__ void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
         }
 
         // ---- accumulate (calc.rs:486-548) the parked entries of every team, entry by entry.  Lane-RELATIVE turns (round 5): lane ln
-        // reads the rows of ITS terms j = ln, ln + 1, ... (row j + 1 = {nx_t, nx_w, nx_e of turn j + 1, A[j]}), four per group, and
+        // reads the rows of ITS terms j = ln, ln + 1, ... (row j + 1: the values of turn j + 1 and A[j], see above), four per group, and
         // drops out (exec mask) once j passes T - 1 -- no term is ever computed to be masked away.  Rounds 1-4 read row j as a
         // broadcast and multiplied the half of the (lane, turn) pairs with j < ln by a select: one v_cndmask per term, its 17
         // compare masks hoisted into SGPR pairs and, at level 0, spilled to VGPR lanes (2 v_readlane per use).
@@ -1665,13 +1689,20 @@ __device__ __noinline__ void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
                     SpF4 r[4];
 #pragma unroll
                     for (int jj = 0; jj < 4; jj++) r[jj] = *reinterpret_cast<const SpF4*>(er + (4 * g + jj) * 4);  // rows past T are zero
+                    // the divisions of two terms at a time (no chain between them), then per term, j ascending, one packed multiply
+                    // and one packed add into (acc_w, acc_e) and the tenpai sum on its own
+                    MjF2 p2[2];
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        const MjF2 a2 = LK == 1 ? MjF2{r[2 * h].z, r[2 * h].w} : MjF2{r[2 * h].w, r[2 * h + 1].w};
+                        p2[h] = sp_div_domain2(a2, my_m, my_r);
+                    }
 #pragma unroll
                     for (int jj = 0; jj < 4; jj++) {
-                        const float prob = sp_div_domain(r[jj].w, my_m, my_r);
+                        const float prob = p2[jj >> 1][jj & 1];
                         if constexpr (LK == 1) acc_t += prob;
-                        else acc_t += prob * r[jj].x;
-                        acc_w += prob * r[jj].y;
-                        acc_e += prob * r[jj].z;
+                        else acc_t += prob * r[jj].z;
+                        acc_we += mj_f2(prob) * MjF2{r[jj].x, r[jj].y};
                     }
                 }
             });
@@ -1680,7 +1711,7 @@ __device__ __noinline__ void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
 
         // ---- end of a state: its values, then the pipeline moves up
         if (done) {
-            sp_st3(nodeB, SP_EL_SLOT(s0) * (u32)sizeof(SpNode) + val_ln, acc_t, acc_w, acc_e);
+            sp_st3(nodeB, SP_EL_SLOT(s0) * (u32)sizeof(SpNode) + val_ln, acc_t, acc_we[0], acc_we[1]);
             s0 = s1; s1 = s2; s2 = s3; s3 = s4;
             h0 = h1; h1 = h2; h2 = h3;
             m_raw = m_nxt; m_nxt = m_n2;
@@ -1689,7 +1720,8 @@ __device__ __noinline__ void sp_eval_wave(SpWork* W, SpCtx* X, float* WL, int fi
             c0 = 0;
             my_m = m_raw != 0.f ? m_raw : 1.f;
             my_r = sp_rcp_refined(my_m);
-            acc_t = acc_w = acc_e = 0.f;
+            acc_t = 0.f;
+            acc_we = MjF2{0.f, 0.f};
             i += stride;
             has = i < end;
         }

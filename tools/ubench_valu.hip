@@ -16,12 +16,12 @@
     OP(a0) OP(a1) OP(a2) OP(a3) OP(a4) OP(a5) OP(a6) OP(a7)
 
 enum Kind { K_ADD, K_AND, K_BFE, K_CNDMASK, K_LSHR64, K_LSHL64, K_MUL_LO, K_MUL_U24, K_MAD_U24, K_BCNT, K_MIN3, K_LSHL_ADD_U64,
-            K_MAD_U64_U32, K_FMA_F32, K_MUL_F32, K_ADD_F32, K_PK_FMA_F32, K_RCP_F32, K_CMP_U32, K_LSHL_ADD_U32, K_PERM, K_ALIGNBIT,
+            K_MAD_U64_U32, K_FMA_F32, K_MUL_F32, K_ADD_F32, K_PK_FMA_F32, K_PK_MUL_F32, K_PK_ADD_F32, K_RCP_F32, K_CMP_U32, K_LSHL_ADD_U32, K_PERM, K_ALIGNBIT,
             K_FFBL, K_ADD_CO, K_SALU_ADD, K_SALU_AND64, K_DS_READ_B32, K_DS_READ_B64, K_DS_WRITE_B32, K_MOV_DPP, K_READLANE, K_N };
 static const char* kind_name[K_N] = {
     "v_add_u32", "v_and_b32", "v_bfe_u32", "v_cndmask_b32", "v_lshrrev_b64", "v_lshlrev_b64", "v_mul_lo_u32", "v_mul_u32_u24",
     "v_mad_u32_u24", "v_bcnt_u32_b32", "v_min3_i32", "v_lshl_add_u64", "v_mad_u64_u32", "v_fma_f32", "v_mul_f32", "v_add_f32",
-    "v_pk_fma_f32", "v_rcp_f32", "v_cmp_lt_u32(vcc)", "v_lshl_add_u32", "v_perm_b32", "v_alignbit_b32", "v_ffbl_b32", "v_add_co_u32",
+    "v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32", "v_rcp_f32", "v_cmp_lt_u32(vcc)", "v_lshl_add_u32", "v_perm_b32", "v_alignbit_b32", "v_ffbl_b32", "v_add_co_u32",
     "s_add_u32", "s_and_b64", "ds_read_b32", "ds_read_b64", "ds_write_b32", "v_mov_b32 dpp row_shr", "v_readlane_b32"};
 
 template <int KIND>
@@ -34,6 +34,7 @@ __global__ __launch_bounds__(256) void k_bench(int iters, uint32_t seed, unsigne
     float f0 = a0 * 1e-9f, f1 = a1 * 1e-9f, f2 = a2 * 1e-9f, f3 = a3 * 1e-9f, f4 = a4 * 1e-9f, f5 = a5 * 1e-9f, f6 = a6 * 1e-9f, f7 = a7 * 1e-9f;
     uint32_t k = seed | 1, sh = (seed & 7) + 1;
     float fk = 1.0000001f;
+    const uint64_t fk2 = (uint64_t)__float_as_uint(fk) * 0x100000001ull;  // {fk, fk}: the second operand of the packed f32 kinds
     uint32_t s0 = seed, s1 = seed + 1, s2 = seed + 2, s3 = seed + 3;
     uint64_t t0 = seed, t1 = seed + 5;
     lds[threadIdx.x] = a0; lds[threadIdx.x + 256] = a1;
@@ -108,6 +109,14 @@ __global__ __launch_bounds__(256) void k_bench(int iters, uint32_t seed, unsigne
         } else if constexpr (KIND == K_PK_FMA_F32) {
 #define OP(x) asm volatile("v_pk_fma_f32 %0, %0, %1, %1" : "+v"(x) : "v"(b7));
             REP8(OP(b0) OP(b1) OP(b2) OP(b3) OP(b4) OP(b5) OP(b6) OP(b0))
+#undef OP
+        } else if constexpr (KIND == K_PK_MUL_F32) {
+#define OP(x) asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(x) : "v"(fk2));
+            REP8(OP(b0) OP(b1) OP(b2) OP(b3) OP(b4) OP(b5) OP(b6) OP(b7))
+#undef OP
+        } else if constexpr (KIND == K_PK_ADD_F32) {
+#define OP(x) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(x) : "v"(fk2));
+            REP8(OP(b0) OP(b1) OP(b2) OP(b3) OP(b4) OP(b5) OP(b6) OP(b7))
 #undef OP
         } else if constexpr (KIND == K_RCP_F32) {
 #define OP(x) asm volatile("v_rcp_f32 %0, %0" : "+v"(x));
@@ -203,18 +212,18 @@ int run_kind(int iters, unsigned long long* d_cyc, uint32_t* d_sink) {
 }
 
 template <int K>
-int run_all(int iters, unsigned long long* d_cyc, uint32_t* d_sink) {
+int run_all(int iters, unsigned long long* d_cyc, uint32_t* d_sink, const char* only) {
     if constexpr (K < K_N) {
-        if (run_kind<K>(iters, d_cyc, d_sink)) return 1;
-        return run_all<K + 1>(iters, d_cyc, d_sink);
+        if ((!only || strstr(kind_name[K], only)) && run_kind<K>(iters, d_cyc, d_sink)) return 1;
+        return run_all<K + 1>(iters, d_cyc, d_sink, only);
     }
     return 0;
 }
 
-int main() {
+int main(int argc, char** argv) {  // ubench_valu [substring]: only the instructions whose name contains it (e.g. _f32)
     unsigned long long* d_cyc;
     uint32_t* d_sink;
     CHECK(hipMalloc(&d_cyc, 64));
     CHECK(hipMalloc(&d_sink, 64));
-    return run_all<0>(20000, d_cyc, d_sink);
+    return run_all<0>(20000, d_cyc, d_sink, argc > 1 ? argv[1] : nullptr);
 }
