@@ -18,6 +18,9 @@
 //              draw_without_tegawari (calc.rs:447-561) with the reference's exact loop order (draw tiles ascending, aka
 //              after its plain tile; i, j ascending) and fold discards like discard_slow (calc.rs:563-637);
 //   write    : the whole SP block of the decision (123 rows; the encoder stops at row 890): sp_block_write.
+// sp_kernel_body (the body of mj_k_sp, mj_k_sp_promo and mj_k_sp_wide) is the driver over these phases, one function each: the next row
+// (sp_wide_next_row, sp_handoff_get) -> sp_row_front -> sp_row_begin -> the expansion loop (sp_park_row / sp_handoff_put in mj_k_sp_promo) ->
+// sp_l0_items, sp_eval_level -> sp_row_write -> sp_row_account; behind the row loop sp_wg_flush and the queue's tail, sp_tail_rows.
 // Work area per workgroup (SpWork): by hash slot only the tags and the 256-byte value nodes; keys, headers and level lists
 // dense by list index (creation order), child lists / level-0 work items / their scores in append-only pools.
 // Memoisation in the reference is a pure cache, so evaluating every reachable state exactly once gives bit-identical
@@ -1934,210 +1937,210 @@ __device__ __forceinline__ SpRowInfo sp_row_front(RowsP rows, SnapP snap, SpWork
     R.n_cand = 0;
     const uint32_t desc = rows[row];
     const int table = ROW_TABLE(desc), p = ROW_SEAT(desc);
-        {
-            const auto src = reinterpret_cast<typename SpF4Of<SnapP>::type>(snap + table);
-            SpRec* d4 = reinterpret_cast<SpRec*>(st);
-            for (int i = tid; i < (int)(sizeof(TableOne) / 16); i += NT) d4[i] = spt_load(&src[i]);
-        }
-        sp_sync<WAVE>();
-        LaneT<TableOne> L;
-        L.B = st;
-        L.l = 0;
-        L.T = &c_mj_tables;
-        const u32 cans = F1(cans, p);
-        const bool can_discard0 = (cans & CAN_DISCARD) != 0;
-        const Hand h0 = load_hand(L, p);
-        const int ld3 = F1(len_div3, p);
-        const int tiles_left = F(tiles_left);
+    {
+        const auto src = reinterpret_cast<typename SpF4Of<SnapP>::type>(snap + table);
+        SpRec* d4 = reinterpret_cast<SpRec*>(st);
+        for (int i = tid; i < (int)(sizeof(TableOne) / 16); i += NT) d4[i] = spt_load(&src[i]);
+    }
+    sp_sync<WAVE>();
+    LaneT<TableOne> L;
+    L.B = st;
+    L.l = 0;
+    L.T = &c_mj_tables;
+    const u32 cans = F1(cans, p);
+    const bool can_discard0 = (cans & CAN_DISCARD) != 0;
+    const Hand h0 = load_hand(L, p);
+    const int ld3 = F1(len_div3, p);
+    const int tiles_left = F(tiles_left);
 
-        // ---- single_player_tables preconditions (agent_helper.rs:509-530) + real_time_shanten (:467-503)
-        int cur_shanten;
-        {
-            const int sh = F1(shanten, p);
-            if (!can_discard0) cur_shanten = sh;
-            else if (sh > 0) cur_shanten = F1(has_next_shanten, p) ? sh - 1 : sh;
-            else if (F1(last_self_tsumo, p) != MJ_NONE) cur_shanten = ((F1(waits, p) >> deaka(F1(last_self_tsumo, p))) & 1) ? -1 : 0;
-            else cur_shanten = calc_all(c_mj_tables, h0, ld3);
-        }
-        int tsumos_left, calc_haitei;
-        if (can_discard0) {
-            tsumos_left = tiles_left / 4;
-            calc_haitei = tiles_left % 4 == 0;
-        } else {
-            int target = (F1(cans_target, p) + 4 - p) & 3;
-            int at_next = max(tiles_left - (4 - target), 0);
-            tsumos_left = at_next / 4;
-            calc_haitei = at_next % 4 == 0;
-        }
-        const bool ok = tiles_left >= 4 && cur_shanten >= 0 && tsumos_left >= 1;
-        R.ok = ok;
-        sp_sync<WAVE>();
-        if (!ok) {
-            // Err path (obs_repr.rs:612-623): max EV = minimal tsumo agari points, everything else zero
-            if (tid == 0) {
-                float v = 0.f;
-                if (cans & CAN_AGARI) {
-                    const bool is_ron = (cans & CAN_RON_AGARI) != 0;
-                    if ((is_ron && (cans & CAN_RON_AGARI)) || (cans & CAN_TSUMO_AGARI)) {
-                        Point pt;
-                        if (seat_agari_points(L, p, is_ron, 0, pt)) v = (float)tsumo_total(pt, p == (F(kyoku) & 3));
-                    }
-                }
-                X.cand_ev0[0] = v;
-            }
-            sp_sync<WAVE>();
-            const float v = X.cand_ev0[0];
-            sp_block_write<WAVE, NT>(out, tid, fminf(fmaxf(v, 0.f), 100000.f) / 100000.f, fminf(fmaxf(v, 0.f), 30000.f) / 30000.f, (const u64*)nullptr,
-                                     (const u64*)nullptr, false, false, (const signed char*)nullptr, (const float*)nullptr, (const int*)nullptr, 0);
-            sp_sync<WAVE>();
-            return R;
-        }
-
-        // ---- calculator set-up (agent_helper.rs:532-586, calc.rs:84-167)
-        bool can_discard = can_discard0;
-        SpState root;
-        root.h = h0;
-        int akas_hand = F1(akas_in_hand, p) & 7;
-        const bool after_riichi = can_discard0 && accepted(L, p);
-        const int last_tsumo = F1(last_self_tsumo, p);
-        if (after_riichi) {
-            root.h.dec(deaka(last_tsumo));
-            if (is_aka(last_tsumo)) akas_hand &= ~(1 << (last_tsumo - T_5MR));
-            can_discard = false;
-        }
-        int n_left_all = 0;
-        {
-            Hand w = {0, 0};
-            for (int t = 0; t < 34; t++) {
-                int seen = F1(pub_seen, t) + h0.get(t);  // tiles_seen = public + own hand (incl. the tile just drawn)
-                int left = (4 - seen) & 7;
-                for (int k = 0; k < left; k++) w.inc(t);
-                n_left_all += left;
-            }
-            root.w = w;
-            int akas_seen = (F(pub_aka_seen) | F1(akas_in_hand, p)) & 7;
-            root.akas = (u32)akas_hand | ((u32)(~akas_seen & 7) << 3);
-        }
-        const int T = tsumos_left, n_left = n_left_all & 0xFF;
-        // fewer draws left than the shanten number: tenpai / win / EV are exactly zero for every candidate (reaching tenpai
-        // takes cur_shanten draws), so neither the probability table nor the state graph are needed at all
-        const bool with_probs = cur_shanten <= 3 && T >= cur_shanten;
-        // Three independent chains of dependent table walks / LDS reads run SIDE BY SIDE on three wavefronts of the workgroup
-        // (one after the other they were 6 + 10 + 10 us of a row's set-up, with 255 threads waiting at the barriers in between):
-        //   lane CTX   : the calculator's constants;
-        //   lane 0     : the discards that keep the shanten number -> the candidate list;
-        //   lanes SPEC : the required draws of root - d for EVERY held kind d, before it is known which d are candidates.
-        constexpr int CTX = (!WAVE && NT > 128) ? 128 : 0, SPEC = (!WAVE && NT > 64) ? 64 : 0;
-        if (tid == CTX) {
-            X.melds = load_melds(L, p);
-            X.len_div3 = ld3;
-            X.bakaze = table_bakaze(L);
-            X.jikaze = seat_jikaze(L, p);
-            X.is_menzen = (F1(pflags, p) & PF_IS_MENZEN) != 0;
-            X.n_dora = F(n_dora_ind);
-            for (int i = 0; i < 5; i++) X.dora_ind[i] = i < X.n_dora ? F1(dora_ind, i) : T_UNK;
-            // num_doras_in_fuuro (agent_helper.rs:533-545) = doras_owned[0] - doras in hand - akas in hand
-            int nf = 0;
-            if (!(X.is_menzen && F1(ankan_n, p) == 0)) {
-                int fn = F1(fuuro_n, p);
-                for (int k = 0; k < fn; k++)
-                    for (int j = 0; j < 4; j++) {
-                        int t = F3(fuuro, p, k, j);
-                        if (t != MJ_NONE) nf += dora_factor(L, deaka(t)) + (is_aka(t) ? 1 : 0);
-                    }
-                int na = F1(ankan_n, p);
-                for (int k = 0; k < na; k++) {
-                    int t = F2(ankan, p, k);
-                    nf += 4 * dora_factor(L, t) + ((t == T_5M || t == T_5P || t == T_5S) ? 1 : 0);
-                }
-            }
-            X.num_doras_in_fuuro = nf & 0xFF;
-            X.prefer_riichi = F1(scores, p) >= 1000;
-            X.calc_double_riichi = can_discard0 && (F1(pflags, p) & PF_CAN_W_RIICHI) != 0;
-            X.calc_haitei = calc_haitei;
-            X.T = T;
-            X.n_left = n_left;
-            X.n_list = 0;
-            X.n_pool = 0;
-            X.n_items = 0;  // (a row without level 0 never sets it)
-            X.overflow = 0;
-            X.prof = prof;
-            for (int k = 0; k < 8; k++) X.pt[k] = 0;
-            for (int l = 0; l < 5; l++) X.lvl_begin[l] = X.lvl_end[l] = 0;
-        }
-        if (with_probs) {  // build_tsumo_prob_table (calc.rs:135-146); the not_tsumo rows come from the shared table c_sp_nt
-            for (int q = tid; q < 4 * SP_T; q += NT) {
-                int i = q / SP_T, j = q % SP_T;
-                X.tsumo_prob[i][j] = j < T ? (float)(i + 1) / (float)(n_left - j) : 0.f;
-            }
-        }
-
-        // ---- candidates: analyze_discard / analyze_draw (+ *_simple for shanten > 3)  (calc.rs:205-312), from the table-id
-        // sets of mj_sptab.h: the discards of the root hand that keep its shanten number, and the draws that lower the shanten
-        // number of root - d (state.rs:176-200)
-        const SpTabG TG = sp_tab_g(c_sp_tab);
-        if (tid >= SPEC && tid < SPEC + 34) {
-            const int d = tid - SPEC;
-            if (can_discard) {
-                if (root.h.get(d)) {
-                    Hand hc = root.h;
-                    hc.dec(d);
-                    X.spec_req[0][d] = sp_req_of_hand(TG, c_mj_tables, hc, ld3, cur_shanten);  // d keeps the shanten number
-                    if (cur_shanten > 3) X.spec_req[1][d] = sp_req_of_hand(TG, c_mj_tables, hc, ld3, cur_shanten + 1);  // d gives one up
-                }
-            } else if (d == 0) {
-                X.spec_req[0][0] = sp_req_of_hand(TG, c_mj_tables, root.h, ld3, calc_all(c_mj_tables, root.h, ld3));
-            }
-        }
+    // ---- single_player_tables preconditions (agent_helper.rs:509-530) + real_time_shanten (:467-503)
+    int cur_shanten;
+    {
+        const int sh = F1(shanten, p);
+        if (!can_discard0) cur_shanten = sh;
+        else if (sh > 0) cur_shanten = F1(has_next_shanten, p) ? sh - 1 : sh;
+        else if (F1(last_self_tsumo, p) != MJ_NONE) cur_shanten = ((F1(waits, p) >> deaka(F1(last_self_tsumo, p))) & 1) ? -1 : 0;
+        else cur_shanten = calc_all(c_mj_tables, h0, ld3);
+    }
+    int tsumos_left, calc_haitei;
+    if (can_discard0) {
+        tsumos_left = tiles_left / 4;
+        calc_haitei = tiles_left % 4 == 0;
+    } else {
+        int target = (F1(cans_target, p) + 4 - p) & 3;
+        int at_next = max(tiles_left - (4 - target), 0);
+        tsumos_left = at_next / 4;
+        calc_haitei = at_next % 4 == 0;
+    }
+    const bool ok = tiles_left >= 4 && cur_shanten >= 0 && tsumos_left >= 1;
+    R.ok = ok;
+    sp_sync<WAVE>();
+    if (!ok) {
+        // Err path (obs_repr.rs:612-623): max EV = minimal tsumo agari points, everything else zero
         if (tid == 0) {
-            int n = 0;
-            if (can_discard) {
-                const u64 keepers = sp_keep_of_hand(TG, c_mj_tables, root.h, ld3, cur_shanten);  // calc_all(root - d) == cur_shanten
-                for (int d = 0; d < 34; d++) {
-                    int c = root.h.get(d);
-                    if (c == 0) continue;
-                    const bool keeps = (keepers >> d) & 1;
-                    int dt = d;
-                    if (d == T_5M && (root.akas & 1) && c == 1) dt = T_5MR;
-                    else if (d == T_5P && (root.akas & 2) && c == 1) dt = T_5PR;
-                    else if (d == T_5S && (root.akas & 4) && c == 1) dt = T_5SR;
-                    if (cur_shanten <= 3 && !keeps) continue;
-                    X.cand_tile[n] = dt;
-                    X.cand_down[n] = cur_shanten > 3 && !keeps;
-                    n++;
+            float v = 0.f;
+            if (cans & CAN_AGARI) {
+                const bool is_ron = (cans & CAN_RON_AGARI) != 0;
+                if ((is_ron && (cans & CAN_RON_AGARI)) || (cans & CAN_TSUMO_AGARI)) {
+                    Point pt;
+                    if (seat_agari_points(L, p, is_ron, 0, pt)) v = (float)tsumo_total(pt, p == (F(kyoku) & 3));
                 }
-            } else {
-                X.cand_tile[0] = T_UNK;
-                X.cand_down[0] = 0;
-                n = 1;
             }
-            X.n_cand = n;
+            X.cand_ev0[0] = v;
         }
         sp_sync<WAVE>();
-        const int n_cand = X.n_cand;
-        if (tid < n_cand) {
-            const u64 spec = can_discard ? X.spec_req[X.cand_down[tid]][deaka(X.cand_tile[tid])] : X.spec_req[0][0];
-            const u64 req = spec & root.w.nonzero_mask();  // the discard does not change the wall
-            int nreq = 0;
-            for (u64 rest = req; rest; rest &= rest - 1) nreq += root.w.get(__ffsll((long long)rest) - 1);
-            X.cand_req[tid] = req;
-            X.cand_nreq[tid] = nreq & 0xFF;
-            X.cand_slot[tid] = -1;
-            X.cand_tp0[tid] = X.cand_wp0[tid] = X.cand_ev0[tid] = 0.f;
-        }
+        const float v = X.cand_ev0[0];
+        sp_block_write<WAVE, NT>(out, tid, fminf(fmaxf(v, 0.f), 100000.f) / 100000.f, fminf(fmaxf(v, 0.f), 30000.f) / 30000.f, (const u64*)nullptr,
+                                 (const u64*)nullptr, false, false, (const signed char*)nullptr, (const float*)nullptr, (const int*)nullptr, 0);
         sp_sync<WAVE>();
-        R.cans = cans;
-        R.can_discard0 = can_discard0;
-        R.can_discard = can_discard;
-        R.after_riichi = after_riichi;
-        R.last_tsumo = last_tsumo;
-        R.cur_shanten = cur_shanten;
-        R.T = T;
-        R.n_cand = n_cand;
-        R.ld3 = ld3;
-        R.root = root;
-        R.with_probs = with_probs;
         return R;
+    }
+
+    // ---- calculator set-up (agent_helper.rs:532-586, calc.rs:84-167)
+    bool can_discard = can_discard0;
+    SpState root;
+    root.h = h0;
+    int akas_hand = F1(akas_in_hand, p) & 7;
+    const bool after_riichi = can_discard0 && accepted(L, p);
+    const int last_tsumo = F1(last_self_tsumo, p);
+    if (after_riichi) {
+        root.h.dec(deaka(last_tsumo));
+        if (is_aka(last_tsumo)) akas_hand &= ~(1 << (last_tsumo - T_5MR));
+        can_discard = false;
+    }
+    int n_left_all = 0;
+    {
+        Hand w = {0, 0};
+        for (int t = 0; t < 34; t++) {
+            int seen = F1(pub_seen, t) + h0.get(t);  // tiles_seen = public + own hand (incl. the tile just drawn)
+            int left = (4 - seen) & 7;
+            for (int k = 0; k < left; k++) w.inc(t);
+            n_left_all += left;
+        }
+        root.w = w;
+        int akas_seen = (F(pub_aka_seen) | F1(akas_in_hand, p)) & 7;
+        root.akas = (u32)akas_hand | ((u32)(~akas_seen & 7) << 3);
+    }
+    const int T = tsumos_left, n_left = n_left_all & 0xFF;
+    // fewer draws left than the shanten number: tenpai / win / EV are exactly zero for every candidate (reaching tenpai
+    // takes cur_shanten draws), so neither the probability table nor the state graph are needed at all
+    const bool with_probs = cur_shanten <= 3 && T >= cur_shanten;
+    // Three independent chains of dependent table walks / LDS reads run SIDE BY SIDE on three wavefronts of the workgroup
+    // (one after the other they were 6 + 10 + 10 us of a row's set-up, with 255 threads waiting at the barriers in between):
+    //   lane CTX   : the calculator's constants;
+    //   lane 0     : the discards that keep the shanten number -> the candidate list;
+    //   lanes SPEC : the required draws of root - d for EVERY held kind d, before it is known which d are candidates.
+    constexpr int CTX = (!WAVE && NT > 128) ? 128 : 0, SPEC = (!WAVE && NT > 64) ? 64 : 0;
+    if (tid == CTX) {
+        X.melds = load_melds(L, p);
+        X.len_div3 = ld3;
+        X.bakaze = table_bakaze(L);
+        X.jikaze = seat_jikaze(L, p);
+        X.is_menzen = (F1(pflags, p) & PF_IS_MENZEN) != 0;
+        X.n_dora = F(n_dora_ind);
+        for (int i = 0; i < 5; i++) X.dora_ind[i] = i < X.n_dora ? F1(dora_ind, i) : T_UNK;
+        // num_doras_in_fuuro (agent_helper.rs:533-545) = doras_owned[0] - doras in hand - akas in hand
+        int nf = 0;
+        if (!(X.is_menzen && F1(ankan_n, p) == 0)) {
+            int fn = F1(fuuro_n, p);
+            for (int k = 0; k < fn; k++)
+                for (int j = 0; j < 4; j++) {
+                    int t = F3(fuuro, p, k, j);
+                    if (t != MJ_NONE) nf += dora_factor(L, deaka(t)) + (is_aka(t) ? 1 : 0);
+                }
+            int na = F1(ankan_n, p);
+            for (int k = 0; k < na; k++) {
+                int t = F2(ankan, p, k);
+                nf += 4 * dora_factor(L, t) + ((t == T_5M || t == T_5P || t == T_5S) ? 1 : 0);
+            }
+        }
+        X.num_doras_in_fuuro = nf & 0xFF;
+        X.prefer_riichi = F1(scores, p) >= 1000;
+        X.calc_double_riichi = can_discard0 && (F1(pflags, p) & PF_CAN_W_RIICHI) != 0;
+        X.calc_haitei = calc_haitei;
+        X.T = T;
+        X.n_left = n_left;
+        X.n_list = 0;
+        X.n_pool = 0;
+        X.n_items = 0;  // (a row without level 0 never sets it)
+        X.overflow = 0;
+        X.prof = prof;
+        for (int k = 0; k < 8; k++) X.pt[k] = 0;
+        for (int l = 0; l < 5; l++) X.lvl_begin[l] = X.lvl_end[l] = 0;
+    }
+    if (with_probs) {  // build_tsumo_prob_table (calc.rs:135-146); the not_tsumo rows come from the shared table c_sp_nt
+        for (int q = tid; q < 4 * SP_T; q += NT) {
+            int i = q / SP_T, j = q % SP_T;
+            X.tsumo_prob[i][j] = j < T ? (float)(i + 1) / (float)(n_left - j) : 0.f;
+        }
+    }
+
+    // ---- candidates: analyze_discard / analyze_draw (+ *_simple for shanten > 3)  (calc.rs:205-312), from the table-id
+    // sets of mj_sptab.h: the discards of the root hand that keep its shanten number, and the draws that lower the shanten
+    // number of root - d (state.rs:176-200)
+    const SpTabG TG = sp_tab_g(c_sp_tab);
+    if (tid >= SPEC && tid < SPEC + 34) {
+        const int d = tid - SPEC;
+        if (can_discard) {
+            if (root.h.get(d)) {
+                Hand hc = root.h;
+                hc.dec(d);
+                X.spec_req[0][d] = sp_req_of_hand(TG, c_mj_tables, hc, ld3, cur_shanten);  // d keeps the shanten number
+                if (cur_shanten > 3) X.spec_req[1][d] = sp_req_of_hand(TG, c_mj_tables, hc, ld3, cur_shanten + 1);  // d gives one up
+            }
+        } else if (d == 0) {
+            X.spec_req[0][0] = sp_req_of_hand(TG, c_mj_tables, root.h, ld3, calc_all(c_mj_tables, root.h, ld3));
+        }
+    }
+    if (tid == 0) {
+        int n = 0;
+        if (can_discard) {
+            const u64 keepers = sp_keep_of_hand(TG, c_mj_tables, root.h, ld3, cur_shanten);  // calc_all(root - d) == cur_shanten
+            for (int d = 0; d < 34; d++) {
+                int c = root.h.get(d);
+                if (c == 0) continue;
+                const bool keeps = (keepers >> d) & 1;
+                int dt = d;
+                if (d == T_5M && (root.akas & 1) && c == 1) dt = T_5MR;
+                else if (d == T_5P && (root.akas & 2) && c == 1) dt = T_5PR;
+                else if (d == T_5S && (root.akas & 4) && c == 1) dt = T_5SR;
+                if (cur_shanten <= 3 && !keeps) continue;
+                X.cand_tile[n] = dt;
+                X.cand_down[n] = cur_shanten > 3 && !keeps;
+                n++;
+            }
+        } else {
+            X.cand_tile[0] = T_UNK;
+            X.cand_down[0] = 0;
+            n = 1;
+        }
+        X.n_cand = n;
+    }
+    sp_sync<WAVE>();
+    const int n_cand = X.n_cand;
+    if (tid < n_cand) {
+        const u64 spec = can_discard ? X.spec_req[X.cand_down[tid]][deaka(X.cand_tile[tid])] : X.spec_req[0][0];
+        const u64 req = spec & root.w.nonzero_mask();  // the discard does not change the wall
+        int nreq = 0;
+        for (u64 rest = req; rest; rest &= rest - 1) nreq += root.w.get(__ffsll((long long)rest) - 1);
+        X.cand_req[tid] = req;
+        X.cand_nreq[tid] = nreq & 0xFF;
+        X.cand_slot[tid] = -1;
+        X.cand_tp0[tid] = X.cand_wp0[tid] = X.cand_ev0[tid] = 0.f;
+    }
+    sp_sync<WAVE>();
+    R.cans = cans;
+    R.can_discard0 = can_discard0;
+    R.can_discard = can_discard;
+    R.after_riichi = after_riichi;
+    R.last_tsumo = last_tsumo;
+    R.cur_shanten = cur_shanten;
+    R.T = T;
+    R.n_cand = n_cand;
+    R.ld3 = ld3;
+    R.root = root;
+    R.with_probs = with_probs;
+    return R;
 }
 
 // Sorting of the candidates + the encoder block of obs v4 (rows 889..1011).
@@ -2146,113 +2149,113 @@ __device__ __forceinline__ void sp_row_write(const SpNode* nodes, SpCtx& X, cons
     const int n_cand = R.n_cand, cur_shanten = R.cur_shanten, T = R.T, last_tsumo = R.last_tsumo;
     const bool with_probs = R.with_probs && tv_area != nullptr;  // (the queue tail of mj_k_sp: rows without a state graph, no staging area)
     const bool can_discard0 = R.can_discard0, after_riichi = R.after_riichi;
-        // ---- sort (calc.rs:181-188 / 196-199) + encode (obs_repr.rs:564-692)
-        if (tid < n_cand) {  // one lane per candidate fetches its turn-0 values (side by side, not a chain of dependent loads)
-            const int c = tid;
-            X.order[c] = c;
-            const int slot = X.cand_slot[c];
-            if (with_probs && slot >= 0) {  // Candidate::from clamps (candidate.rs:46-70); shanten 0 => tenpai = 1
-                const SpNode& nd = nodes[slot];
-                const float tp = cur_shanten == 0 ? 1.f : nd.val[0][0];
-                X.cand_tp0[c] = fminf(fmaxf(tp, 0.f), 1.f);
-                X.cand_wp0[c] = fminf(fmaxf(nd.val[0][1], 0.f), 1.f);
-                X.cand_ev0[c] = fmaxf(nd.val[0][2], 0.f);
-            }
+    // ---- sort (calc.rs:181-188 / 196-199) + encode (obs_repr.rs:564-692)
+    if (tid < n_cand) {  // one lane per candidate fetches its turn-0 values (side by side, not a chain of dependent loads)
+        const int c = tid;
+        X.order[c] = c;
+        const int slot = X.cand_slot[c];
+        if (with_probs && slot >= 0) {  // Candidate::from clamps (candidate.rs:46-70); shanten 0 => tenpai = 1
+            const SpNode& nd = nodes[slot];
+            const float tp = cur_shanten == 0 ? 1.f : nd.val[0][0];
+            X.cand_tp0[c] = fminf(fmaxf(tp, 0.f), 1.f);
+            X.cand_wp0[c] = fminf(fmaxf(nd.val[0][1], 0.f), 1.f);
+            X.cand_ev0[c] = fmaxf(nd.val[0][2], 0.f);
         }
-        sp_sync<WAVE>();
-        if (tid == 0) {
-            auto cmp = [&](int l, int r, int by) -> int {  // candidate.rs:73-106, by: 0 EV, 3 NotShantenDown
-                if (X.cand_tile[l] == X.cand_tile[r]) return 0;
-                int o;
-                if (by <= 0 && (o = f32_total_cmp(X.cand_ev0[l], X.cand_ev0[r])) != 0) return o;
-                if (by <= 1 && (o = f32_total_cmp(X.cand_wp0[l], X.cand_wp0[r])) != 0) return o;
-                if (by <= 2 && (o = f32_total_cmp(X.cand_tp0[l], X.cand_tp0[r])) != 0) return o;
-                if (!X.cand_down[l] && X.cand_down[r]) return 1;
-                if (X.cand_down[l] && !X.cand_down[r]) return -1;
-                if (X.cand_nreq[l] != X.cand_nreq[r]) return X.cand_nreq[l] < X.cand_nreq[r] ? -1 : 1;
-                return cmp_discard_priority(X.cand_tile[l], X.cand_tile[r]);
-            };
-            const int by = with_probs ? 0 : 3;
-            for (int i = 1; i < n_cand; i++) {  // stable insertion sort, descending: before(l, r) = cmp(r, l) < 0
-                int v = X.order[i], j = i - 1;
-                while (j >= 0 && cmp(X.order[j], v, by) < 0) {
-                    X.order[j + 1] = X.order[j];
-                    j--;
-                }
-                X.order[j + 1] = v;
+    }
+    sp_sync<WAVE>();
+    if (tid == 0) {
+        auto cmp = [&](int l, int r, int by) -> int {  // candidate.rs:73-106, by: 0 EV, 3 NotShantenDown
+            if (X.cand_tile[l] == X.cand_tile[r]) return 0;
+            int o;
+            if (by <= 0 && (o = f32_total_cmp(X.cand_ev0[l], X.cand_ev0[r])) != 0) return o;
+            if (by <= 1 && (o = f32_total_cmp(X.cand_wp0[l], X.cand_wp0[r])) != 0) return o;
+            if (by <= 2 && (o = f32_total_cmp(X.cand_tp0[l], X.cand_tp0[r])) != 0) return o;
+            if (!X.cand_down[l] && X.cand_down[r]) return 1;
+            if (X.cand_down[l] && !X.cand_down[r]) return -1;
+            if (X.cand_nreq[l] != X.cand_nreq[r]) return X.cand_nreq[l] < X.cand_nreq[r] ? -1 : 1;
+            return cmp_discard_priority(X.cand_tile[l], X.cand_tile[r]);
+        };
+        const int by = with_probs ? 0 : 3;
+        for (int i = 1; i < n_cand; i++) {  // stable insertion sort, descending: before(l, r) = cmp(r, l) < 0
+            int v = X.order[i], j = i - 1;
+            while (j >= 0 && cmp(X.order[j], v, by) < 0) {
+                X.order[j + 1] = X.order[j];
+                j--;
             }
-            // the candidate with the most required tiles: Iterator::max_by keeps the LAST maximum (obs_repr.rs:589-596)
-            int best = -1;
-            for (int k = 0; k < n_cand; k++) {
-                int c = X.order[k];
-                if (best < 0 || cmp(c, best, 3) >= 0) best = c;
-            }
-            X.lvl_begin[4] = best;
+            X.order[j + 1] = v;
         }
+        // the candidate with the most required tiles: Iterator::max_by keeps the LAST maximum (obs_repr.rs:589-596)
+        int best = -1;
+        for (int k = 0; k < n_cand; k++) {
+            int c = X.order[k];
+            if (best < 0 || cmp(c, best, 3) >= 0) best = c;
+        }
+        X.lvl_begin[4] = best;
+    }
+    sp_sync<WAVE>();
+    {
+        const int first = n_cand > 0 ? X.order[0] : -1;
+        const float max_ev = (with_probs && first >= 0 && T > 0) ? X.cand_ev0[first] : 0.f;
+        // ---- the masks of block rows 2 .. 71 (required tiles), one 34-bit word per output row
+        u64* const rowm = &X.spec_req[0][0];  // (the set-up's speculative sets are consumed)
+        static_assert(sizeof(X.spec_req) == 68 * sizeof(u64), "block rows 2 .. 69 = [keep / shanten-down][34 discards]");
+        for (int i = tid; i < 68; i += NT) rowm[i] = 0ull;  // (NT = 64 for the rows a single wavefront processes)
+        if (tid < 2) X.row7x[tid] = 0ull;
+        if (tid < 34) X.colcand[tid] = -1;
         sp_sync<WAVE>();
-        {
-            const int first = n_cand > 0 ? X.order[0] : -1;
-            const float max_ev = (with_probs && first >= 0 && T > 0) ? X.cand_ev0[first] : 0.f;
-            // ---- the masks of block rows 2 .. 71 (required tiles), one 34-bit word per output row
-            u64* const rowm = &X.spec_req[0][0];  // (the set-up's speculative sets are consumed)
-            static_assert(sizeof(X.spec_req) == 68 * sizeof(u64), "block rows 2 .. 69 = [keep / shanten-down][34 discards]");
-            for (int i = tid; i < 68; i += NT) rowm[i] = 0ull;  // (NT = 64 for the rows a single wavefront processes)
-            if (tid < 2) X.row7x[tid] = 0ull;
-            if (tid < 34) X.colcand[tid] = -1;
-            sp_sync<WAVE>();
-            if (can_discard0 && !after_riichi) {
-                if (tid < n_cand) {
-                    const int dtid = deaka(X.cand_tile[tid]);
-                    rowm[(X.cand_down[tid] ? 34 : 0) + dtid] = X.cand_req[tid];
-                    X.colcand[dtid] = (signed char)tid;
-                }
-                if (tid == 0 && X.lvl_begin[4] >= 0) X.row7x[0] = 1ull << deaka(X.cand_tile[X.lvl_begin[4]]);
-            } else if (can_discard0) {
-                // discard after riichi: `cans.can_discard` is still true in the encoder (obs_repr.rs:580), the single
-                // candidate's tile was patched to the drawn tile (agent_helper.rs:588-590)
-                if (tid == 0) {
-                    if (first >= 0) rowm[deaka(last_tsumo)] = X.cand_req[first];
-                    X.row7x[0] = 1ull << deaka(last_tsumo);
-                    if (n_cand > 0) X.colcand[deaka(last_tsumo)] = 0;
-                }
-            } else {
-                if (tid == 0 && first >= 0) X.row7x[1] = X.cand_req[first];
+        if (can_discard0 && !after_riichi) {
+            if (tid < n_cand) {
+                const int dtid = deaka(X.cand_tile[tid]);
+                rowm[(X.cand_down[tid] ? 34 : 0) + dtid] = X.cand_req[tid];
+                X.colcand[dtid] = (signed char)tid;
             }
-            // sp table (obs_repr.rs:644-692)
-            const float ev_scale = max_ev < 1.f ? 0.f : 1.f / max_ev;
-            bool table_ok = with_probs && first >= 0 && X.cand_tp0[first] > 0.f;
-            float* tv = tv_area;  // [candidate slot * SP_T + turn][4]: tenpai, win, ev, alive
-            if (table_ok) {  // uniform over the workgroup
-                // one load per (candidate, turn): the clamped values go to the LDS (the evaluation scratch is free now), and
-                // take_while(p > 0) on the tenpai probs becomes a count of the leading positive turns
-                static_assert(SP_EVAL_LDS_FLOATS(64) >= SP_MAX_CAND * SP_T * 4, "table staging fits the evaluation scratch");
-                const int n_src = can_discard0 ? n_cand : 1;
-                for (int q = tid; q < n_src * SP_T; q += NT) {
-                    const int c = q / SP_T, turn = q % SP_T;
-                    {
-                        float tpv = 0.f, wpv = 0.f, evv = 0.f;
-                        if (turn < T) {
-                            const SpNode& nd = nodes[X.cand_slot[can_discard0 ? c : first]];
-                            tpv = cur_shanten == 0 ? 1.f : fminf(fmaxf(nd.val[turn][0], 0.f), 1.f);
-                            wpv = fminf(fmaxf(nd.val[turn][1], 0.f), 1.f);
-                            evv = fmaxf(nd.val[turn][2], 0.f);
-                        }
-                        float* dst = tv + (c * SP_T + turn) * 4;
-                        dst[0] = tpv; dst[1] = wpv; dst[2] = fminf(evv * ev_scale, 1.f); dst[3] = tpv > 0.f ? 1.f : 0.f;
+            if (tid == 0 && X.lvl_begin[4] >= 0) X.row7x[0] = 1ull << deaka(X.cand_tile[X.lvl_begin[4]]);
+        } else if (can_discard0) {
+            // discard after riichi: `cans.can_discard` is still true in the encoder (obs_repr.rs:580), the single
+            // candidate's tile was patched to the drawn tile (agent_helper.rs:588-590)
+            if (tid == 0) {
+                if (first >= 0) rowm[deaka(last_tsumo)] = X.cand_req[first];
+                X.row7x[0] = 1ull << deaka(last_tsumo);
+                if (n_cand > 0) X.colcand[deaka(last_tsumo)] = 0;
+            }
+        } else {
+            if (tid == 0 && first >= 0) X.row7x[1] = X.cand_req[first];
+        }
+        // sp table (obs_repr.rs:644-692)
+        const float ev_scale = max_ev < 1.f ? 0.f : 1.f / max_ev;
+        bool table_ok = with_probs && first >= 0 && X.cand_tp0[first] > 0.f;
+        float* tv = tv_area;  // [candidate slot * SP_T + turn][4]: tenpai, win, ev, alive
+        if (table_ok) {  // uniform over the workgroup
+            // one load per (candidate, turn): the clamped values go to the LDS (the evaluation scratch is free now), and
+            // take_while(p > 0) on the tenpai probs becomes a count of the leading positive turns
+            static_assert(SP_EVAL_LDS_FLOATS(64) >= SP_MAX_CAND * SP_T * 4, "table staging fits the evaluation scratch");
+            const int n_src = can_discard0 ? n_cand : 1;
+            for (int q = tid; q < n_src * SP_T; q += NT) {
+                const int c = q / SP_T, turn = q % SP_T;
+                {
+                    float tpv = 0.f, wpv = 0.f, evv = 0.f;
+                    if (turn < T) {
+                        const SpNode& nd = nodes[X.cand_slot[can_discard0 ? c : first]];
+                        tpv = cur_shanten == 0 ? 1.f : fminf(fmaxf(nd.val[turn][0], 0.f), 1.f);
+                        wpv = fminf(fmaxf(nd.val[turn][1], 0.f), 1.f);
+                        evv = fmaxf(nd.val[turn][2], 0.f);
                     }
-                }
-                sp_sync<WAVE>();
-                if (tid < n_src) {  // (the node slots are read: cand_slot now holds the candidates' alive counts)
-                    int n_alive = 0;
-                    while (n_alive < SP_T && tv[(tid * SP_T + n_alive) * 4 + 3] != 0.f) n_alive++;
-                    X.cand_slot[tid] = n_alive;
+                    float* dst = tv + (c * SP_T + turn) * 4;
+                    dst[0] = tpv; dst[1] = wpv; dst[2] = fminf(evv * ev_scale, 1.f); dst[3] = tpv > 0.f ? 1.f : 0.f;
                 }
             }
             sp_sync<WAVE>();
-            sp_block_write<WAVE, NT>(out, tid, fminf(fmaxf(max_ev, 0.f), 100000.f) / 100000.f, fminf(fmaxf(max_ev, 0.f), 30000.f) / 30000.f,
-                                     (const u64*)rowm, (const u64*)X.row7x, table_ok, !can_discard0, (const signed char*)X.colcand, (const float*)tv,
-                                     (const int*)X.cand_slot, T);
+            if (tid < n_src) {  // (the node slots are read: cand_slot now holds the candidates' alive counts)
+                int n_alive = 0;
+                while (n_alive < SP_T && tv[(tid * SP_T + n_alive) * 4 + 3] != 0.f) n_alive++;
+                X.cand_slot[tid] = n_alive;
+            }
         }
+        sp_sync<WAVE>();
+        sp_block_write<WAVE, NT>(out, tid, fminf(fmaxf(max_ev, 0.f), 100000.f) / 100000.f, fminf(fmaxf(max_ev, 0.f), 30000.f) / 30000.f,
+                                 (const u64*)rowm, (const u64*)X.row7x, table_ok, !can_discard0, (const signed char*)X.colcand, (const float*)tv,
+                                 (const int*)X.cand_slot, T);
+    }
 }
 
 // A row without a state graph (queue tail, sp_row_class == 7), processed by ONE wavefront with its own context: set-up and encoder only.
@@ -2312,6 +2315,43 @@ static_assert(sizeof(SpHandoff) <= SP_HANDOFF_WORDS * 4 && sizeof(SpHandoff) % 4
 #define SP_ACQUIRE_AGENT() ((void)0)
 #define SP_SPIN_PAUSE() ((void)0)
 #endif
+// Producer (mj_k_sp_promo, the whole workgroup): the context, R, the row, the level to go on with and the area's tag epoch go to the area's
+// hand-off block; then drain, barrier, lane 0 releases and publishes `entry` (work area + 1).
+template <int NT>
+__device__ __forceinline__ void sp_handoff_put(SpWork* W, const SpCtx& X, const SpRowInfo& R, const int tid, const int row, const int next_lv,
+                                               const unsigned tag_epoch, int* entry, const int area) {
+    const u32* sx = reinterpret_cast<const u32*>(&X);
+    SP_HBM u32* dst = (SP_HBM u32*)W->handoff;
+    for (int i = tid; i < (int)(sizeof(SpCtx) / 4); i += NT) dst[i] = sx[i];
+    if (tid == 0) {
+        SpHandoff* H = reinterpret_cast<SpHandoff*>(W->handoff);
+        H->R = R;
+        H->row = row;
+        H->next_lv = next_lv;
+        W->epoch = tag_epoch;
+    }
+    // every wavefront's stores of this row (nodes, keys, lists, pools ...) are in L2 before lane 0 releases them
+    SP_DRAIN_STORES();
+    __syncthreads();
+    if (tid == 0) {
+        SP_RELEASE_AGENT();
+        __hip_atomic_store(entry, area + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// Consumer (mj_k_sp_wide, the whole workgroup, behind lane 0's acquire and the workgroup barrier that follow the poll in sp_kernel_body):
+// the context comes back from the block, with R, the row and the level to go on with; the tag epoch is the context's.
+template <int NT>
+__device__ __forceinline__ void sp_handoff_get(SpWork* W, SpCtx& X, const int tid, SpRowInfo& R, int& row, int& next_lv, unsigned& tag_epoch) {
+    SP_HBM const u32* src = (SP_HBM const u32*)W->handoff;
+    u32* dx = reinterpret_cast<u32*>(&X);
+    for (int i = tid; i < (int)(sizeof(SpCtx) / 4); i += NT) dx[i] = src[i];
+    const SpHandoff* H = reinterpret_cast<const SpHandoff*>(W->handoff);
+    R = H->R;
+    row = H->row;
+    next_lv = H->next_lv;
+    __syncthreads();
+    tag_epoch = X.tag_epoch;
+}
 
 template <int NT>
 struct SpLds {
@@ -2323,6 +2363,267 @@ struct SpLds {
     };
 };
 
+// ---- the phases of one row, in the order sp_kernel_body runs them.  None takes the kernel's parameter block (see sp_row_front): its fields
+// come by value.
+
+// mj_k_sp_wide, lane 0 -- the next row: a promoted one if there is any (the largest first), else one from the row queue like mj_k_sp -- a wide
+// workgroup never idles while rows are left; when the queue is empty it waits for promotions until every producer has gone.
+// Returns > 0: promoted (work area + 1); < 0: -(queue position + 1); 0: nothing left.
+// main_done / drained: the row queue is empty / the last look at the promotion queues (the only state across calls).
+__device__ __forceinline__ int sp_wide_next_row(int* queue, unsigned long long* err, const int promo_cap, const int sweep, const int n_narrow,
+                                                const int n_heavy, bool& main_done, bool& drained) {
+    int got = 0;
+    const int cap = promo_cap / SP_PROMO_LEVELS;
+    long long t_idle = 0;
+    for (;;) {
+        for (int q = 0; q < SP_PROMO_LEVELS && !got; q++) {
+            int* const ents = queue + SP_Q_PROMO_ENT + q * (SP_PROMO_CAP / SP_PROMO_LEVELS);
+            int* const head = queue + SP_Q_PROMO_HEAD(q) + (sweep ? 1 : 0);
+            for (;;) {
+                const int h = __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int a = min(__hip_atomic_load(queue + SP_Q_PROMO_ALLOC(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), cap);
+                if (h >= a) break;
+                if (atomicCAS(head, h, h + 1) != h) continue;
+                // entry h is ours; its producer publishes it right behind the allocation (a copy + one release)
+                const long long t_w = wall_clock64();
+                int e;
+                while ((e = __hip_atomic_load(ents + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0 && !sweep &&
+                       wall_clock64() - t_w < SP_WIDE_TIMEOUT)
+                    SP_SPIN_PAUSE();
+                if (e == 0 && !sweep) atomicAdd(&err[SP_ERR_WIDE_GAVEUP], 1ull);  // (left to the sweep)
+                if (e > 0 && atomicCAS(ents + h, e, -1) == e) {       // (the sweep skips what the first launch took)
+                    got = e;
+                    break;
+                }
+            }
+        }
+        if (got || sweep) break;
+        if (!main_done) {
+            const int r = atomicAdd(queue, 1);
+            if (r < n_heavy) {
+                got = -(r + 1);
+                break;
+            }
+            main_done = true;
+        }
+        // nothing to do right now.  Every producer gone (their entries were released before they arrived at the DONE word) and
+        // still nothing => finished
+        if (__hip_atomic_load(queue + SP_Q_PROMO_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n_narrow) {
+            if (drained) break;
+            drained = true;  // (one more look at the queues)
+            continue;
+        }
+        const long long now = wall_clock64();
+        if (t_idle == 0) t_idle = now;
+        else if (now - t_idle > SP_WIDE_TIMEOUT) {  // the two kernels do not overlap (or mj_k_sp has not started): give up, the sweep follows
+            atomicAdd(&err[SP_ERR_WIDE_GAVEUP], 1ull);
+            break;
+        }
+        SP_SPIN_PAUSE();
+    }
+    return got;
+}
+
+// mj_k_sp_promo, promotion: this level (n_states = its size) is large (the ones below it will be larger) and a wide workgroup may take the row
+// from here.  Returns the spare area of this promotion, where the workgroup goes on (the row is parked in W), or nullptr: expand the level here.
+// (The spare area comes back as a value: with W and tag_epoch updated in here through references mj_k_sp_promo spills more VGPRs.)
+template <int NT>
+__device__ __forceinline__ SpWork* sp_park_row(SpWork* W, const unsigned tag_epoch, SpWork* work, int* queue, int& s_k, const SpCtx& X,
+                                               const SpRowInfo& R, const int tid, const int row, const int lv, const int n_states,
+                                               const int promo_cap, const int promo_min) {
+    if (!(promo_cap > 0 && lv < R.cur_shanten && n_states >= promo_min && !X.overflow)) return nullptr;
+    const int pq = n_states >= 2 * promo_min ? 0 : 1;  // the largest rows have their own queue: wide workgroups take them first
+    if (tid == 0) s_k = atomicAdd(queue + SP_Q_PROMO_ALLOC(pq), 1);
+    __syncthreads();
+    const int k = s_k;
+    if (k >= promo_cap / SP_PROMO_LEVELS) return nullptr;
+    sp_handoff_put<NT>(W, X, R, tid, row, lv, tag_epoch, queue + SP_Q_PROMO_ENT + pq * (SP_PROMO_CAP / SP_PROMO_LEVELS) + k, (int)(W - work));
+    return work + gridDim.x + pq * (promo_cap / SP_PROMO_LEVELS) + k;
+}
+
+// Row begin: the epochs of the child cache and of the hash tags (or their wipes), then the root states = level cur_shanten.  A row taken
+// over from another workgroup (promoted) brings its tags and levels along and only resets its share of the pass timers.
+template <int NT, bool LDS_SET>
+__device__ __forceinline__ void sp_row_begin(SpWork* W, SpCtx& X, u64* s_set, const SpState& root, const int n_cand, const bool can_discard,
+                                             const int cur_shanten, const int tid, const bool promoted, unsigned long long* prof,
+                                             unsigned& n_graph_rows, unsigned& tag_epoch) {
+    if constexpr (!LDS_SET) {
+        // a new row = a new epoch of the child cache (8 bits, 1..255; when they have gone round the cache is wiped)
+        n_graph_rows++;
+        if ((n_graph_rows & 255u) == 0u) {
+            n_graph_rows++;
+            for (int i = tid; i < SP_SET_SLOTS; i += NT) s_set[i] = 0ull;
+        }
+    }
+    if (tid == 0) {
+        X.set = s_set;
+        X.cc_epoch = n_graph_rows & 255u;
+    }
+    if (promoted) {
+        if (tid == 0) {
+            X.prof = prof;
+            for (int k = 0; k < 8; k++) X.pt[k] = 0ull;  // (the first workgroup flushed its share of the pass timers)
+        }
+        __syncthreads();
+    } else {
+        // a new row = a new epoch of the hash tags
+        if (tag_epoch >= SP_EPOCH_WRAP) {  // wrapped (once in 2 M rows): wipe the table, start over
+            for (int i = tid; i < SP_CAP; i += NT) W->tag[i] = 0ull;
+            if constexpr (LDS_SET)  // (the set's ways carry the same epoch)
+                for (int i = tid; i < SP_SET_SLOTS; i += NT) s_set[i] = 0ull;
+            tag_epoch = 0;
+            __syncthreads();
+        }
+        tag_epoch++;
+        if (tid == 0) X.tag_epoch = tag_epoch;
+        __syncthreads();
+        // root states = level cur_shanten
+        if (tid < n_cand) {  // one lane per candidate: the claims (one L2 atomic round trip each) run side by side
+            const int c = tid;
+            SpState s = root;
+            if (can_discard) sp_discard(s, X.cand_tile[c]);
+            X.cand_slot[c] = sp_insert<LDS_SET>(W, &X, sp_dk_add(0ull, -1, can_discard ? X.cand_tile[c] : -1), s, -1, -1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            X.lvl_begin[cur_shanten] = 0;
+            X.lvl_end[cur_shanten] = X.n_list;
+        }
+        __syncthreads();
+    }
+}
+
+// Level 0's win items: the probe pass over the states [b, e), then the scoring of every item.  Returns the clock between the two (the
+// caller keeps the level-0 sub-phase timers: with their updates in here mj_k_sp's instruction stream changes).
+template <int NT>
+__device__ __forceinline__ long long sp_l0_items(SpWork* W, SpCtx& X, SpChunk* wchunk, const int tid, const int b, const int e) {
+    if (tid == 0) X.n_items = 0;
+    __syncthreads();
+    const int ns = min(SP_NS, max(1, (e - b + NT / SP_NT - 1) / (NT / SP_NT)));
+    for (int c0 = b + ns * (tid / SP_NT); c0 < e; c0 += ns * (NT / SP_NT))
+        sp_l0_probe_chunk(W, &X, &wchunk[tid / SP_NT], c0, min(ns, e - c0));
+    __syncthreads();
+    const long long t_2a = wall_clock64();
+    const int n_items = min(X.n_items, SP_ITEMS);
+    if ((tid & ~63) < n_items) sp_l0_score_all(W, &X, n_items, tid, NT);  // (a wavefront without items: no call)
+    __syncthreads();
+    return t_2a;
+}
+
+// Evaluation of level lv = list entries [b, e), sorted by cost first.
+template <int NT>
+__device__ __forceinline__ void sp_eval_level(SpWork* W, SpCtx& X, float* ev, unsigned long long* s_stat, const int tid, const int lv, const int b,
+                                              const int e, const int cur_shanten, const int T, const bool prof) {
+    sp_sort_level<NT>(W, reinterpret_cast<int*>(ev), b, e);
+    // teams of exactly T lanes, floor(64 / T) per wavefront (the leftover lanes of a wavefront idle)
+    // ... of the turns that can be reached at this level: the first `off` turns are dead
+    const int off = min(cur_shanten - lv, T - 1), TW = T - off;
+    const int wl = tid & 63, tw = wl / TW, ln = wl - tw * TW;
+    float* wl_lds = ev + (tid >> 6) * SP_EVW_WAVE_FLOATS;
+    const long long t_ev0 = prof ? wall_clock64() : 0;
+    if (lv == 0) {
+        const int tpw0 = min(64 / TW, SP_EVW_WAVE_FLOATS / (SP_EV_ENT * SP_EV0_STRIDE));
+        const int team0 = (tid >> 6) * tpw0 + tw, n_teams0 = (NT / 64) * tpw0;
+        const bool on0 = tw < tpw0;
+        if (b + (tid >> 6) * tpw0 >= e) {}  // no state for any team of this wavefront: no call (14-20 callee-saved VGPRs saved / restored each)
+        else if (T <= 8) sp_eval_wave0<8>(W, &X, wl_lds, b + team0, e, n_teams0, ln, off, tw, on0);
+        else if (T <= 16) sp_eval_wave0<16>(W, &X, wl_lds, b + team0, e, n_teams0, ln, off, tw, on0);
+        else sp_eval_wave0<17>(W, &X, wl_lds, b + team0, e, n_teams0, ln, off, tw, on0);
+    } else {
+        // levels > 0: the whole wavefront in lock-step (sp_eval_wave), its own team geometry (LDS per team differs)
+        const int tpw2 = min(64 / TW, SP_EVW_WAVE_FLOATS / sp_evw_team_floats(T));
+        const int team2 = (tid >> 6) * tpw2 + tw, n_teams2 = (NT / 64) * tpw2;
+        const bool on = tw < tpw2;
+        if (b + (tid >> 6) * tpw2 >= e) {}  // (see level 0)
+        else if (T <= 8) {
+            if (lv == 1) sp_eval_wave<8, 1>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
+            else sp_eval_wave<8, 2>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
+        } else if (T <= 16) {
+            if (lv == 1) sp_eval_wave<16, 1>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
+            else sp_eval_wave<16, 2>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
+        } else {
+            if (lv == 1) sp_eval_wave<17, 1>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
+            else sp_eval_wave<17, 2>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
+        }
+    }
+    if (prof && (tid & 63) == 0) atomicAdd(&s_stat[SP_ERR_T_EVAL_WAVE], (unsigned long long)(wall_clock64() - t_ev0));  // wavefront time inside the evaluation (all levels)
+    __syncthreads();
+}
+
+// Row statistics (thread 0, behind the row's last barrier) into the workgroup's share s_stat.  t_0 .. t_5: the row's phase boundaries
+// (start, set-up done, expanded, level 0 done, evaluated, written), plain values like leaf_dead: a struct of them, or the clock read or
+// the condition spelled out in here, changes mj_k_sp's instruction stream.
+__device__ __forceinline__ void sp_row_account(unsigned long long* s_stat, const SpCtx& X, const long long t_0, const long long t_1,
+                                               const long long t_2, const long long t_3, const long long t_4, const long long t_5,
+                                               const bool parked, const bool with_probs, const bool leaf_dead, const bool prof) {
+    if (!parked) s_stat[SP_ERR_ROWS] += 1ull;
+    if (leaf_dead) s_stat[SP_ERR_STATS] += 1ull;
+    s_stat[SP_ERR_T_SETUP] += (unsigned long long)(t_1 - t_0);
+    if (with_probs) {
+        s_stat[SP_ERR_T_EXPAND] += (unsigned long long)(t_2 - t_1);
+        if (!parked) {
+            s_stat[SP_ERR_T_EVAL0] += (unsigned long long)(t_3 - t_2);
+            s_stat[SP_ERR_T_EVAL] += (unsigned long long)(t_4 - t_3);
+            s_stat[SP_ERR_T_WRITE] += (unsigned long long)(t_5 - t_4);
+            s_stat[SP_ERR_STATES] += (unsigned long long)X.n_list;
+            s_stat[SP_ERR_EDGES] += (unsigned long long)X.n_pool;
+            s_stat[SP_ERR_L0_ITEMS] += (unsigned long long)X.n_items;
+        }
+        if (prof)
+            for (int k = 0; k < 7; k++) s_stat[SP_ERR_PASS + k] += X.pt[k];
+        if (prof) s_stat[SP_ERR_T_L0_PROBE] += X.pt[7];
+    }
+}
+
+// The workgroup's statistics, once, behind its last row (see sp_light_row for why not per row).  MJ_SP_PROF: t_wg0 / c_wg0 = its start in
+// wall-clock ticks / shader-clock cycles (lifetime: SP_ERR_WG_LIFE .. SP_ERR_WG_CLOCK), t_pop / t_reset = its queue + reset time.
+__device__ __forceinline__ void sp_wg_flush(unsigned long long* s_stat, unsigned long long* err, const int tid, const bool prof, const long long t_wg0,
+                                            const long long c_wg0, const long long t_pop, const long long t_reset) {
+    if (prof && tid == 0) {
+        const unsigned long long life = (unsigned long long)(wall_clock64() - t_wg0);
+        s_stat[SP_ERR_WG_LIFE] += life;
+#ifndef MJ_EMU
+        s_stat[SP_ERR_WG_CLOCK] += (unsigned long long)(clock64() - c_wg0);
+#endif
+        atomicMax(&err[SP_ERR_WG_LIFE_MAX], life);
+        s_stat[SP_ERR_T_POP] += (unsigned long long)t_pop;
+        s_stat[SP_ERR_T_RESET] += (unsigned long long)t_reset;
+    }
+    __syncthreads();  // (every thread leaves the row loop at the same pop)
+    if (tid < SP_ERR_STATS && tid != SP_ERR_WG_LIFE_MAX && s_stat[tid]) atomicAdd(&err[tid], s_stat[tid]);
+    if (tid == SP_ERR_STATS && s_stat[tid]) atomicAdd(&err[SP_ERR_DEAD_LEAF], s_stat[tid]);
+}
+
+// ---- the tail of the queue: every wavefront takes its own rows (set-up + encoder only, no workgroup barrier any more)
+// The tail has its own head word (another 128-byte line than the heavy rows' head) and is popped SP_TAIL_BATCH rows at a time:
+// ~46 k light rows per launch against 4,096 wavefronts that need ~10 us per row ask for ~400 pops per microsecond, and one word
+// serves ~88 (MI355X_MICROARCH.md, dequeue row) -- one row per atomic made the tail dequeue-bound.
+__device__ __forceinline__ void sp_tail_rows(const uint32_t* rows, const TableOne* snap, float* obs, SpWork* W, SpWaveArea* wave, int* queue,
+                                             const uint32_t* order, unsigned long long* err, const int n_rows, const int n_heavy, const int tid) {
+    const int wv = tid >> 6, lane = tid & 63;
+    unsigned long long w_rows = 0, w_ticks = 0, w_over = 0;
+    for (;;) {
+        int q = 0;
+        if (lane == 0) q = n_heavy + atomicAdd(queue + SP_Q_TAIL, SP_TAIL_BATCH);
+        q = __shfl(q, 0);
+        if (q >= n_rows) break;
+        const int qe = min(q + SP_TAIL_BATCH, n_rows);
+        for (; q < qe; q++) {
+            const unsigned long long r = sp_light_row(rows, snap, obs, W, &wave[wv], (int)order[q]);
+            w_rows++;
+            w_ticks += r & 0x7FFFFFFFFFFFFFFFull;
+            w_over += r >> 63;
+        }
+    }
+    if (lane == 0 && w_rows) {  // the wavefront's statistics, once
+        atomicAdd(&err[SP_ERR_ROWS], w_rows);
+        atomicAdd(&err[SP_ERR_T_SETUP], w_ticks);
+        if (w_over) atomicAdd(&err[SP_ERR_OVERFLOW], w_over);
+    }
+}
+
+// One persistent workgroup of mj_k_sp (WIDE = PROMO = false), mj_k_sp_promo (PROMO) or mj_k_sp_wide (WIDE).  Per row:
+// pop or take over -> set-up -> begin -> expand (or park) -> evaluate -> write -> account; then the statistics and the queue's tail.
 template <int NT, bool WIDE, bool PROMO>
 __device__ __forceinline__ void sp_kernel_body(SpParams P) {
     __shared__ SpCtx X;
@@ -2344,11 +2645,13 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
     // the hash tags start empty (zeroed once when the work area is allocated); a row's tags carry its epoch, no row clears anything
     unsigned tag_epoch = W->epoch;  // (uniform; written back when the workgroup leaves the row loop / parks a row)
     unsigned own_epoch = tag_epoch;  // (mj_k_sp_wide: the epoch of its own area while it works in a promoted row's)
-    bool main_done = false, drained = false;  // (mj_k_sp_wide, lane 0: the row queue is empty; the last look at the promotion queues)
+    bool main_done = false, drained = false;  // (mj_k_sp_wide, lane 0: sp_wide_next_row's state)
 
     const long long t_wg0 = P.prof ? wall_clock64() : 0;  // MJ_SP_PROF: workgroup lifetime / queue + reset time (SP_ERR_WG_LIFE .. SP_ERR_T_RESET)
 #ifndef MJ_EMU
     const long long c_wg0 = P.prof ? clock64() : 0;       // the same lifetime in shader-clock cycles (s_memtime, SP_ERR_WG_CLOCK)
+#else
+    const long long c_wg0 = 0;                            // (the emulator has no shader clock)
 #endif
     long long t_pop = 0, t_reset = 0;
     // the queue is ordered by cost class (mj_k_order_*): the rows of class 7 (no state graph at all) form its tail
@@ -2361,59 +2664,10 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         SpRowInfo R;
         long long t_0, t_1, t_2, t_3, t_4;
         bool promoted = false;  // (mj_k_sp_wide only) this row was parked by a workgroup of mj_k_sp: continue it from its hand-off block
+        // ---- pop a row, or (mj_k_sp_wide) take a parked one over
         if constexpr (WIDE) {
-            // ---- the next row: a promoted one if there is any (the largest first), else one from the row queue like mj_k_sp -- a wide
-            // workgroup never idles while rows are left; when the queue is empty it waits for promotions until every producer has gone
             if (tid == 0) {
-                int got = 0;  // > 0: promoted (work area + 1); < 0: -(queue position + 1); 0: nothing left
-                const int cap = P.promo_cap / SP_PROMO_LEVELS;
-                long long t_idle = 0;
-                for (;;) {
-                    for (int q = 0; q < SP_PROMO_LEVELS && !got; q++) {
-                        int* const ents = P.queue + SP_Q_PROMO_ENT + q * (SP_PROMO_CAP / SP_PROMO_LEVELS);
-                        int* const head = P.queue + SP_Q_PROMO_HEAD(q) + (P.sweep ? 1 : 0);
-                        for (;;) {
-                            const int h = __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const int a = min(__hip_atomic_load(P.queue + SP_Q_PROMO_ALLOC(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), cap);
-                            if (h >= a) break;
-                            if (atomicCAS(head, h, h + 1) != h) continue;
-                            // entry h is ours; its producer publishes it right behind the allocation (a copy + one release)
-                            const long long t_w = wall_clock64();
-                            int e;
-                            while ((e = __hip_atomic_load(ents + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0 && !P.sweep &&
-                                   wall_clock64() - t_w < SP_WIDE_TIMEOUT)
-                                SP_SPIN_PAUSE();
-                            if (e == 0 && !P.sweep) atomicAdd(&P.err[SP_ERR_WIDE_GAVEUP], 1ull);  // (left to the sweep)
-                            if (e > 0 && atomicCAS(ents + h, e, -1) == e) {       // (the sweep skips what the first launch took)
-                                got = e;
-                                break;
-                            }
-                        }
-                    }
-                    if (got || P.sweep) break;
-                    if (!main_done) {
-                        const int r = atomicAdd(P.queue, 1);
-                        if (r < n_heavy) {
-                            got = -(r + 1);
-                            break;
-                        }
-                        main_done = true;
-                    }
-                    // nothing to do right now.  Every producer gone (their entries were released before they arrived at the DONE word) and
-                    // still nothing => finished
-                    if (__hip_atomic_load(P.queue + SP_Q_PROMO_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= P.n_narrow) {
-                        if (drained) break;
-                        drained = true;  // (one more look at the queues)
-                        continue;
-                    }
-                    const long long now = wall_clock64();
-                    if (t_idle == 0) t_idle = now;
-                    else if (now - t_idle > SP_WIDE_TIMEOUT) {  // the two kernels do not overlap (or mj_k_sp has not started): give up, the sweep follows
-                        atomicAdd(&P.err[SP_ERR_WIDE_GAVEUP], 1ull);
-                        break;
-                    }
-                    SP_SPIN_PAUSE();
-                }
+                const int got = sp_wide_next_row(P.queue, P.err, P.promo_cap, P.sweep, P.n_narrow, n_heavy, main_done, drained);
                 s_row = got;
                 if (got > 0) SP_ACQUIRE_AGENT();  // the producer's release: this CU reads the area for the first time
             }
@@ -2425,15 +2679,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
                 promoted = true;
                 if (tid == 0) atomicAdd(&P.err[P.sweep ? SP_ERR_SWEPT : SP_ERR_PROMOTED], 1ull);  // rows finished here (by the sweep launch: the two kernels did not overlap)
                 W = P.work + (s_row - 1);
-                SP_HBM const u32* src = (SP_HBM const u32*)W->handoff;
-                u32* dx = reinterpret_cast<u32*>(&X);
-                for (int i = tid; i < (int)(sizeof(SpCtx) / 4); i += NT) dx[i] = src[i];
-                const SpHandoff* H = reinterpret_cast<const SpHandoff*>(W->handoff);
-                R = H->R;
-                row = H->row;
-                lv_first = H->next_lv;
-                __syncthreads();
-                tag_epoch = X.tag_epoch;
+                sp_handoff_get<NT>(W, X, tid, R, row, lv_first, tag_epoch);
             } else {
                 W = W_own;
                 tag_epoch = own_epoch;
@@ -2449,6 +2695,7 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
             t_0 = wall_clock64();
             t_1 = t_2 = t_3 = t_4 = t_0;
         }
+        // ---- set-up
         float* out = P.obs + (size_t)row * (1012 * 34);
         if (!promoted) {
             R = sp_row_front<false, NT>(P.rows, P.snap, W, X, &s_tm.st, tid, row, out, P.prof);
@@ -2469,88 +2716,20 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
         }
         bool parked = false;
         if (with_probs) {
-            if constexpr (!LDS_SET) {
-                // a new row = a new epoch of the child cache (8 bits, 1..255; when they have gone round the cache is wiped)
-                n_graph_rows++;
-                if ((n_graph_rows & 255u) == 0u) {
-                    n_graph_rows++;
-                    for (int i = tid; i < SP_SET_SLOTS; i += NT) s_set[i] = 0ull;
-                }
-            }
-            if (tid == 0) {
-                X.set = s_set;
-                X.cc_epoch = n_graph_rows & 255u;
-            }
-            if (promoted) {
-                if (tid == 0) {
-                    X.prof = P.prof;
-                    for (int k = 0; k < 8; k++) X.pt[k] = 0ull;  // (the first workgroup flushed its share of the pass timers)
-                }
-                __syncthreads();
-            } else {
-                // a new row = a new epoch of the hash tags
-                if (tag_epoch >= SP_EPOCH_WRAP) {  // wrapped (once in 2 M rows): wipe the table, start over
-                    for (int i = tid; i < SP_CAP; i += NT) W->tag[i] = 0ull;
-                    if constexpr (LDS_SET)  // (the set's ways carry the same epoch)
-                        for (int i = tid; i < SP_SET_SLOTS; i += NT) s_set[i] = 0ull;
-                    tag_epoch = 0;
-                    __syncthreads();
-                }
-                tag_epoch++;
-                if (tid == 0) X.tag_epoch = tag_epoch;
-                __syncthreads();
-                // root states = level cur_shanten
-                if (tid < n_cand) {  // one lane per candidate: the claims (one L2 atomic round trip each) run side by side
-                    const int c = tid;
-                    SpState s = root;
-                    if (can_discard) sp_discard(s, X.cand_tile[c]);
-                    X.cand_slot[c] = sp_insert<LDS_SET>(W, &X, sp_dk_add(0ull, -1, can_discard ? X.cand_tile[c] : -1), s, -1, -1);
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    X.lvl_begin[cur_shanten] = 0;
-                    X.lvl_end[cur_shanten] = X.n_list;
-                }
-                __syncthreads();
-            }
-            // expand top-down
+            sp_row_begin<NT, LDS_SET>(W, X, s_set, root, n_cand, can_discard, cur_shanten, tid, promoted, P.prof, n_graph_rows, tag_epoch);
+            // ---- expand top-down
             for (int lv = promoted ? lv_first : cur_shanten; lv >= 1; lv--) {
                 const int b = X.lvl_begin[lv], e = X.lvl_end[lv];
                 if constexpr (PROMO) {  // (mj_k_sp_promo only: compiled into mj_k_sp the parking code costs the full-size pool 2.7 % -- register allocation)
-                    // ---- promotion: this level is large (the ones below it will be larger) and a wide workgroup may take the row from here
-                    if (P.promo_cap > 0 && lv < cur_shanten && e - b >= P.promo_min[lv] && !X.overflow) {
-                        const int pq = e - b >= 2 * P.promo_min[lv] ? 0 : 1;  // the largest rows have their own queue: wide workgroups take them first
-                        if (tid == 0) s_k = atomicAdd(P.queue + SP_Q_PROMO_ALLOC(pq), 1);
-                        __syncthreads();
-                        const int k = s_k;
-                        if (k < P.promo_cap / SP_PROMO_LEVELS) {
-                            {
-                                const u32* sx = reinterpret_cast<const u32*>(&X);
-                                SP_HBM u32* dst = (SP_HBM u32*)W->handoff;
-                                for (int i = tid; i < (int)(sizeof(SpCtx) / 4); i += NT) dst[i] = sx[i];
-                                if (tid == 0) {
-                                    SpHandoff* H = reinterpret_cast<SpHandoff*>(W->handoff);
-                                    H->R = R;
-                                    H->row = row;
-                                    H->next_lv = lv;
-                                    W->epoch = tag_epoch;
-                                }
-                            }
-                            // every wavefront's stores of this row (nodes, keys, lists, pools ...) are in L2 before lane 0 releases them
-                            SP_DRAIN_STORES();
-                            __syncthreads();
-                            if (tid == 0) {
-                                SP_RELEASE_AGENT();
-                                __hip_atomic_store(P.queue + SP_Q_PROMO_ENT + pq * (SP_PROMO_CAP / SP_PROMO_LEVELS) + k, (int)(W - P.work) + 1, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT);
-                            }
-                            W = P.work + gridDim.x + pq * (P.promo_cap / SP_PROMO_LEVELS) + k;  // the spare area of this promotion
-                            tag_epoch = W->epoch;
-                            parked = true;
-                            break;
-                        }
+                    SpWork* const spare = sp_park_row<NT>(W, tag_epoch, P.work, P.queue, s_k, X, R, tid, row, lv, e - b, P.promo_cap, P.promo_min[lv]);
+                    if (spare) {
+                        W = spare;
+                        tag_epoch = W->epoch;
+                        parked = true;
+                        break;
                     }
                 }
+                // expansion of the level, left in here: sp_expand_chunk inlined through a helper of its own changes mj_k_sp's instruction stream.
                 // every wavefront its own chunks; a level too small for four full chunks is split four ways (a chunk pass costs
                 // the same for 4 states as for 16, so idle wavefronts are the only thing to lose)
                 const int ns = min(SP_NS, max(1, (e - b + NT / SP_NT - 1) / (NT / SP_NT)));
@@ -2571,93 +2750,33 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
             t_2 = wall_clock64();
             t_3 = t_2;  // (a row without level 0)
             if (tid == 0 && !parked) sp_emu_check_unique(W, &X);  // (its verdict is read after the row's last barrier)
-            // evaluate bottom-up
+            // ---- evaluate bottom-up
             if (!parked)
-            for (int lv = (cur_shanten >= 1 && T == cur_shanten) ? 1 : 0; lv <= cur_shanten; lv++) {  // (leaf_dead: no probe, no scoring, no sort, no sums)
-                const int b = X.lvl_begin[lv], e = X.lvl_end[lv];
-                if (lv == 0) {
-                    if (tid == 0) X.n_items = 0;
-                    __syncthreads();
-                    const int ns = min(SP_NS, max(1, (e - b + NT / SP_NT - 1) / (NT / SP_NT)));
-                    for (int c0 = b + ns * (tid / SP_NT); c0 < e; c0 += ns * (NT / SP_NT))
-                        sp_l0_probe_chunk(W, &X, &s_tm.wchunk[tid / SP_NT], c0, min(ns, e - c0));
-                    __syncthreads();
-                    const long long t_2a = wall_clock64();
-                    const int n_items = min(X.n_items, SP_ITEMS);
-                    if ((tid & ~63) < n_items) sp_l0_score_all(W, &X, n_items, tid, NT);  // (a wavefront without items: no call)
-                    __syncthreads();
-                    if (P.prof && tid == 0) {  // level-0 sub-phases: probe, scoring (the sum is the rest of the level-0 timer)
-                        X.pt[7] += (unsigned long long)(t_2a - t_2);
-                        s_stat[SP_ERR_T_L0_SCORE] += (unsigned long long)(wall_clock64() - t_2a);
-                    }
-                }
-                sp_sort_level<NT>(W, reinterpret_cast<int*>(s_tm.ev), b, e);
-                {
-                    // teams of exactly T lanes, floor(64 / T) per wavefront (the leftover lanes of a wavefront idle)
-                    // ... of the turns that can be reached at this level: the first `off` turns are dead
-                    const int off = min(cur_shanten - lv, T - 1), TW = T - off;
-                    const int wl = tid & 63, tw = wl / TW, ln = wl - tw * TW;
-                    float* wl_lds = s_tm.ev + (tid >> 6) * SP_EVW_WAVE_FLOATS;
-                    const long long t_ev0 = P.prof ? wall_clock64() : 0;
+                for (int lv = (cur_shanten >= 1 && T == cur_shanten) ? 1 : 0; lv <= cur_shanten; lv++) {  // (leaf_dead: no probe, no scoring, no sort, no sums)
+                    const int b = X.lvl_begin[lv], e = X.lvl_end[lv];
                     if (lv == 0) {
-                        const int tpw0 = min(64 / TW, SP_EVW_WAVE_FLOATS / (SP_EV_ENT * SP_EV0_STRIDE));
-                        const int team0 = (tid >> 6) * tpw0 + tw, n_teams0 = (NT / 64) * tpw0;
-                        const bool on0 = tw < tpw0;
-                        if (b + (tid >> 6) * tpw0 >= e) {}  // no state for any team of this wavefront: no call (14-20 callee-saved VGPRs saved / restored each)
-                        else if (T <= 8) sp_eval_wave0<8>(W, &X, wl_lds, b + team0, e, n_teams0, ln, off, tw, on0);
-                        else if (T <= 16) sp_eval_wave0<16>(W, &X, wl_lds, b + team0, e, n_teams0, ln, off, tw, on0);
-                        else sp_eval_wave0<17>(W, &X, wl_lds, b + team0, e, n_teams0, ln, off, tw, on0);
-                    } else {
-                        // levels > 0: the whole wavefront in lock-step (sp_eval_wave), its own team geometry (LDS per team differs)
-                        const int tpw2 = min(64 / TW, SP_EVW_WAVE_FLOATS / sp_evw_team_floats(T));
-                        const int team2 = (tid >> 6) * tpw2 + tw, n_teams2 = (NT / 64) * tpw2;
-                        const bool on = tw < tpw2;
-                        if (b + (tid >> 6) * tpw2 >= e) {}  // (see level 0)
-                        else if (T <= 8) {
-                            if (lv == 1) sp_eval_wave<8, 1>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
-                            else sp_eval_wave<8, 2>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
-                        } else if (T <= 16) {
-                            if (lv == 1) sp_eval_wave<16, 1>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
-                            else sp_eval_wave<16, 2>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
-                        } else {
-                            if (lv == 1) sp_eval_wave<17, 1>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
-                            else sp_eval_wave<17, 2>(W, &X, wl_lds, b + team2, e, n_teams2, ln, off, tw, on);
+                        const long long t_2a = sp_l0_items<NT>(W, X, s_tm.wchunk, tid, b, e);
+                        if (P.prof && tid == 0) {  // level-0 sub-phases: probe, scoring (the sum is the rest of the level-0 timer)
+                            X.pt[7] += (unsigned long long)(t_2a - t_2);
+                            s_stat[SP_ERR_T_L0_SCORE] += (unsigned long long)(wall_clock64() - t_2a);
                         }
                     }
-                    if (P.prof && (tid & 63) == 0) atomicAdd(&s_stat[SP_ERR_T_EVAL_WAVE], (unsigned long long)(wall_clock64() - t_ev0));  // wavefront time inside the evaluation (all levels)
+                    sp_eval_level<NT>(W, X, s_tm.ev, s_stat, tid, lv, b, e, cur_shanten, T, P.prof != nullptr);
+                    if (lv == 0) t_3 = wall_clock64();
                 }
-                __syncthreads();
-                if (lv == 0) t_3 = wall_clock64();
-            }
             t_4 = wall_clock64();
         }
-
+        // ---- write, account
         if (!parked) sp_row_write<false, NT>(W->node, X, R, tid, out, s_tm.ev);
         __syncthreads();
         if (tid == 0) {
-            long long t_5 = wall_clock64();
-            if (!parked) s_stat[SP_ERR_ROWS] += 1ull;
-            if (!parked && with_probs && cur_shanten >= 1 && T == cur_shanten) s_stat[SP_ERR_STATS] += 1ull;  // leaf_dead
-            s_stat[SP_ERR_T_SETUP] += (unsigned long long)(t_1 - t_0);
-            if (with_probs) {
-                s_stat[SP_ERR_T_EXPAND] += (unsigned long long)(t_2 - t_1);
-                if (!parked) {
-                    s_stat[SP_ERR_T_EVAL0] += (unsigned long long)(t_3 - t_2);
-                    s_stat[SP_ERR_T_EVAL] += (unsigned long long)(t_4 - t_3);
-                    s_stat[SP_ERR_T_WRITE] += (unsigned long long)(t_5 - t_4);
-                    s_stat[SP_ERR_STATES] += (unsigned long long)X.n_list;
-                    s_stat[SP_ERR_EDGES] += (unsigned long long)X.n_pool;
-                    s_stat[SP_ERR_L0_ITEMS] += (unsigned long long)X.n_items;
-                }
-                if (P.prof)
-                    for (int k = 0; k < 7; k++) s_stat[SP_ERR_PASS + k] += X.pt[k];
-                if (P.prof) s_stat[SP_ERR_T_L0_PROBE] += X.pt[7];
-            }
+            const long long t_5 = wall_clock64();
+            sp_row_account(s_stat, X, t_0, t_1, t_2, t_3, t_4, t_5, parked, with_probs, !parked && with_probs && cur_shanten >= 1 && T == cur_shanten, P.prof != nullptr);
         }
         if constexpr (WIDE) {
             if (!promoted) own_epoch = tag_epoch;
         }
-        // ---- the hash set needs no reset (tag epochs); a row that overflowed it is counted
+        // the hash set needs no reset (tag epochs); a row that overflowed it is counted
         const long long t_r = P.prof ? wall_clock64() : 0;
         if (X.overflow && tid == 0 && !parked) s_stat[SP_ERR_OVERFLOW] += 1ull;
         __syncthreads();
@@ -2675,46 +2794,9 @@ __device__ __forceinline__ void sp_kernel_body(SpParams P) {
             }
         }
     }
-    if (P.prof && tid == 0) {
-        const unsigned long long life = (unsigned long long)(wall_clock64() - t_wg0);
-        s_stat[SP_ERR_WG_LIFE] += life;
-#ifndef MJ_EMU
-        s_stat[SP_ERR_WG_CLOCK] += (unsigned long long)(clock64() - c_wg0);
-#endif
-        atomicMax(&P.err[SP_ERR_WG_LIFE_MAX], life);
-        s_stat[SP_ERR_T_POP] += (unsigned long long)t_pop;
-        s_stat[SP_ERR_T_RESET] += (unsigned long long)t_reset;
-    }
-    __syncthreads();  // (every thread leaves the row loop at the same pop)
-    if (tid < SP_ERR_STATS && tid != SP_ERR_WG_LIFE_MAX && s_stat[tid]) atomicAdd(&P.err[tid], s_stat[tid]);  // the workgroup's statistics, once
-    if (tid == SP_ERR_STATS && s_stat[tid]) atomicAdd(&P.err[SP_ERR_DEAD_LEAF], s_stat[tid]);
-    // ---- the tail of the queue: every wavefront takes its own rows (set-up + encoder only, no workgroup barrier any more)
-    // The tail has its own head word (another 128-byte line than the heavy rows' head) and is popped SP_TAIL_BATCH rows at a time:
-    // ~46 k light rows per launch against 4,096 wavefronts that need ~10 us per row ask for ~400 pops per microsecond, and one word
-    // serves ~88 (MI355X_MICROARCH.md, dequeue row) -- one row per atomic made the tail dequeue-bound.
+    sp_wg_flush(s_stat, P.err, tid, P.prof != nullptr, t_wg0, c_wg0, t_pop, t_reset);
     if constexpr (!WIDE) {
-    if (wave_mode) {
-        const int wv = tid >> 6, lane = tid & 63;
-        unsigned long long w_rows = 0, w_ticks = 0, w_over = 0;
-        for (;;) {
-            int q = 0;
-            if (lane == 0) q = n_heavy + atomicAdd(P.queue + SP_Q_TAIL, SP_TAIL_BATCH);
-            q = __shfl(q, 0);
-            if (q >= P.n_rows) break;
-            const int qe = min(q + SP_TAIL_BATCH, P.n_rows);
-            for (; q < qe; q++) {
-                const unsigned long long r = sp_light_row(P.rows, P.snap, P.obs, W, &s_tm.wave[wv], (int)P.order[q]);
-                w_rows++;
-                w_ticks += r & 0x7FFFFFFFFFFFFFFFull;
-                w_over += r >> 63;
-            }
-        }
-        if (lane == 0 && w_rows) {  // the wavefront's statistics, once
-            atomicAdd(&P.err[SP_ERR_ROWS], w_rows);
-            atomicAdd(&P.err[SP_ERR_T_SETUP], w_ticks);
-            if (w_over) atomicAdd(&P.err[SP_ERR_OVERFLOW], w_over);
-        }
-    }
+        if (wave_mode) sp_tail_rows(P.rows, P.snap, P.obs, W, s_tm.wave, P.queue, P.order, P.err, P.n_rows, n_heavy, tid);
     }
 }
 

@@ -3,6 +3,7 @@
 #   tools/pmc_sp.sh <outdir-tag> [tables] [extra bench flags]
 # Output: gpurun_out/<tag>/<pass>.txt with per-launch averages; tools/summarize_sp_pmc.py folds them into profiles/.
 # PMC_SP_PASSES="1 2" restricts the run to those passes (a quick instruction-count / activity check of a kernel variant).
+# The first rocprofv3 run that does not exit 0 (a failure, the 240 s limit) ends the script with that status.
 OUT=/root/repo/gpurun_out/${1:-pmc_sp}; TABLES=${2:-65536}; shift; shift
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 i=0
@@ -15,8 +16,12 @@ for set in \
   "WRITE_SIZE TCP_TCC_READ_REQ_sum"; do
   i=$((i+1)); tag=p$i
   if [ -n "$PMC_SP_PASSES" ] && ! echo " $PMC_SP_PASSES " | grep -q " $i "; then continue; fi
-  timeout 240 rocprofv3 --pmc $set --kernel-include-regex mj_k_sp --output-format csv -d $OUT/$tag -- \
+  timeout -k 10 240 rocprofv3 --pmc $set --kernel-include-regex mj_k_sp --output-format csv -d $OUT/$tag -- \
       python /root/repo/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-matrix --version 4 --tables $TABLES "$@" > $OUT/$tag.log 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then  # a pass that failed or timed out ends the job: nothing more is started on that GPU
+    echo "pass $i ($set): rocprofv3 exited $rc, stopping; the end of $OUT/$tag.log:"; tail -n 5 $OUT/$tag.log; exit $rc
+  fi
   python3 - <<PY | tee $OUT/$tag.txt
 import csv,glob,collections
 fs=glob.glob('$OUT/$tag/*/*counter_collection.csv')
