@@ -1027,6 +1027,10 @@ void mj_emu_sp_placed(uint64_t out[2]) { out[0] = g_sp_emu_placed[0]; out[1] = g
 void mj_emu_sp_lost_claims(uint64_t out[4]) {
     for (int k = 0; k < 2; k++) out[k] = g_sp_emu_lost[2 + k], out[2 + k] = g_sp_emu_lost[k] - g_sp_emu_lost[2 + k];
 }
+// paths of the expansion's insert pass taken since then (mj_sp.hip: g_sp_emu_paths)
+void mj_emu_sp_insert_paths(uint64_t out[6]) {
+    for (int k = 0; k < 6; k++) out[k] = g_sp_emu_paths[k];
+}
 #ifdef MJ_EMU_REGISTRY
 // the emulated runtime's registry (tests/host/emu/hip/hip_runtime.h): live buffers (device and pinned) / events / streams, frees and
 // destroys of something not live, allocations and stream synchronises made since the library was loaded

@@ -378,16 +378,17 @@ MJD int sp_f2i(float v) {
 // (hand, wall)  <->  (draw multiset, discard multiset) is a bijection, and the two sorted multisets, 6 bits per tile
 // (0 = none), are an EXACT 42-bit identifier: two different states of a row never share one, equal states always do.
 // The hash set compares this id, not a hash of the 256-bit key (round 1 accepted a 63-bit hash match).
+template <bool BOTH = false>  // BOTH: the caller has a draw and a discard (no test of either)
 MJD u64 sp_dk_add(u64 dk, int draw_tile, int discard_tile) {  // -1 = none
     u32 d0 = (u32)dk & 63, d1 = (u32)(dk >> 6) & 63, d2 = (u32)(dk >> 12) & 63;
     u32 x0 = (u32)(dk >> 18) & 63, x1 = (u32)(dk >> 24) & 63, x2 = (u32)(dk >> 30) & 63, x3 = (u32)(dk >> 36) & 63;
-    if (draw_tile >= 0) {  // sorted (descending) insertion; the lowest field is free by construction
+    if (BOTH || draw_tile >= 0) {  // sorted (descending) insertion; the lowest field is free by construction
         u32 x = (u32)draw_tile + 1, t;
         t = max(d0, x); x = min(d0, x); d0 = t;
         t = max(d1, x); x = min(d1, x); d1 = t;
         d2 = max(d2, x);
     }
-    if (discard_tile >= 0) {
+    if (BOTH || discard_tile >= 0) {
         u32 x = (u32)discard_tile + 1, t;
         t = max(x0, x); x = min(x0, x); x0 = t;
         t = max(x1, x); x = min(x1, x); x1 = t;
@@ -514,10 +515,16 @@ inline void sp_emu_check_unique(WP W, SpCtx* X) {
 }
 inline unsigned long long g_sp_emu_placed[2];  // states placed in the LDS set / in the HBM table (tests: a small set must send states both ways)
 inline void sp_emu_placed(int k) { g_sp_emu_placed[k]++; }
+// paths of the expansion's insert pass (sp_expand_chunk, P4) taken since the library was loaded: [0] rounds with one entry per lane,
+// [1] with two, [2] entries decoded by the search, [3] claim-loop turns of a lane beyond its first, [4] entries sent to the HBM
+// table, [5] linear-probe steps there
+inline unsigned long long g_sp_emu_paths[6];
+inline void sp_emu_path(int k) { g_sp_emu_paths[k]++; }
 #else
 template <class WP> MJD void sp_emu_check_hit(WP, SpCtx*, u32, u64, const SpState&) {}
 template <class WP> MJD void sp_emu_check_unique(WP, SpCtx*) {}
 MJD void sp_emu_placed(int) {}
+MJD void sp_emu_path(int) {}
 #endif
 // The LDS part of the hash set (mj_k_sp): SP_SET_BUCKETS buckets of two ways, each way a tag as in SpWork::tag (a tag of another epoch
 // is a free way; nothing is cleared between rows).  A state has two buckets; both are read (one ds_read_b128 each, issued together)
@@ -526,6 +533,9 @@ MJD void sp_emu_placed(int) {}
 // ways to the same end, whenever it looks -- two lanes inserting one id in the same round meet at the same way (the loser finds the id
 // there), and a state that found all four ways taken by others (-> the HBM table) is never found or placed here later.
 // Returns the slot (2 * bucket + way) | 1 << 16 if this call claimed it (a fresh state), or -1: not in LDS, and never will be.
+// This function serves the row's root states (sp_insert).  The expansion's insert pass (sp_expand_chunk, stages 2-3) is the same walk
+// for a wavefront's entries at once: the same look, then one way per turn of a loop in the same order, each way read again before its
+// compare-and-swap -- a later look can only find more ways taken, never one freed, so the argument above covers it as it stands.
 __device__ __forceinline__ int sp_set_find_or_claim(u64* set, u32 h, u64 tag, u32 ep) {
     struct alignas(16) Bucket { u64 w[2]; };
     const u32 b[2] = {sp_hash_b1(h), sp_hash_b2(h)};
@@ -1070,7 +1080,8 @@ __device__ __forceinline__ void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C,
             const int sfn = __shfl((pre_ex - base) | (nt_lane << 16), has_item ? my_s : sb);  // (lanes before sb are never asked)
             const int s_first = sfn & 0xFFFF, s_n = sfn >> 16;
             const int s_last = s_first + s_n - 1;
-            const u32 before = __shfl(pv, max(s_first - 1, 0)), upto = __shfl(pv, max(s_last, 0)), all = __shfl(pv, SP_NT - 1);
+            const u32 before = __shfl(pv, max(s_first - 1, 0)), upto = __shfl(pv, max(s_last, 0));
+            const u32 all = (u32)sp_lane_get((int)pv, SP_NT - 1);  // (a scalar: the insert pass branches on the number of entries)
             const u32 base = s_first > 0 ? before : 0u;
             n_entries = (int)(all & 0xFFFFu);
             if (has_item) {
@@ -1107,106 +1118,103 @@ __device__ __forceinline__ void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C,
         mj_team_sync<SP_NT>();
         if (prof) tp3 = wall_clock64();
         // P4: children, one lane per CHILD ENTRY (draw variant x kept discard): it inserts its child state into the hash set and
-        // leaves its child-list entry at its place of the reference's order (t, variant, d ascending).  A lane takes TWO entries
-        // per round and claims both hash slots before it looks at either answer: an insert is one L2 atomic round trip of
-        // latency and little else, so two in flight per lane halve the rounds.
+        // leaves its child-list entry at its place of the reference's order (t, variant, d ascending).  A lane takes TWO entries per
+        // round (a round with at most 64 entries: one), and a round is a short sequence of STAGES that its entries go through together:
+        // a stage is straight-line select code for every lane, and what only some lanes need -- the search for an entry the layout
+        // pass did not decode, a way to claim, the HBM table, a new state's record -- sits behind ONE wavefront-uniform test (a
+        // ballot), so the common round (every child found in the LDS set) runs without a lane-divergent branch.  Written as per-lane
+        // control flow (decode, look, claim, probe and list with their early returns, inlined once per entry) the round compiled to
+        // 1,990 instructions, more than half of them exec-mask bookkeeping: 216 saves, 161 exec branches, each with its conservative wait
+        // (tests/test_sp_insert_isa.py counts both forms).
         struct Ent {  // one child entry, decoded
             bool on;
-            int s, it, local, rank, nk, tile, dt, count;
+            int tile, dt;  // the drawn tile (red variant applied), the discarded tile
+            u32 td;        // the same without the variants: drawn tile | discarded tile << 6 | drawn red << 12 | discarded red << 13 | parent << 14
+            int pos_out;   // its place in the pool
+            u32 ent;       // its child-list entry, all but the slot
             u64 dk;
-            u32 h;  // sp_dk_hash(dk)
+            u32 h;         // sp_dk_hash(dk)
+#ifdef MJ_EMU
+            SpState S;     // the parent (the checks on every hit build the child)
+#endif
         };
-        auto decode = [&](int e) -> Ent {
+        // the einfo word of an entry at or past SP_EINFO_CAP, which the layout pass did not leave: its item by a binary search over
+        // eoff (largest item with eoff[item] <= ee), its discard by a loop over the kept bits
+        auto einfo_search = [&](int ee) -> u32 {
+            int lo = 0, hi = n_items;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if ((int)C->eoff[mid] <= ee) lo = mid; else hi = mid;
+            }
+            const int local = ee - (int)C->eoff[lo];
+            const u64 bits = C->kept[lo];
+            const int nk = __popcll(bits), vidx = local >= nk ? 1 : 0, rank = local - vidx * nk;
+            u64 mrest = bits;
+            for (int r = rank; r > 0; r--) mrest &= mrest - 1;
+            sp_emu_path(2);
+            return (u32)lo | ((u32)(__ffsll((long long)mrest) - 1) << 6) | ((u32)vidx << 12) | (rank == nk - 1 ? 1u << 13 : 0u);
+        };
+        auto decode = [&](int e, u32 w) -> Ent {  // w: the entry's einfo word (an entry past the end decodes entry 0 and stays off)
             Ent E;
             E.on = e < n_entries;
-            const int ee = E.on ? e : 0;
-            int lo, vidx, d;
-            if (ee < SP_EINFO_CAP) {  // decoded by the layout pass
-                const u32 w = C->einfo[ee];
-                lo = (int)(w & 63u);
-                d = (int)((w >> 6) & 63u);
-                vidx = (int)((w >> 12) & 1u);
-                E.local = ee - (int)C->eoff[lo];
-                E.nk = 2;                                // only `rank == nk - 1` (the last discard of the draw entry) is asked of these two
-                E.rank = (w >> 13) & 1u ? 1 : 0;
-            } else {
-                lo = 0;
-                int hi = n_items;  // largest item with eoff[item] <= e
-                while (hi - lo > 1) {
-                    const int mid = (lo + hi) >> 1;
-                    if ((int)C->eoff[mid] <= ee) lo = mid; else hi = mid;
-                }
-                E.local = ee - (int)C->eoff[lo];
-                const u64 bits = C->kept[lo];
-                E.nk = __popcll(bits);
-                vidx = E.local >= E.nk ? 1 : 0;
-                E.rank = E.local - vidx * E.nk;
-                u64 mrest = bits;
-                for (int r = E.rank; r > 0; r--) mrest &= mrest - 1;
-                d = __ffsll((long long)mrest) - 1;
-            }
-            E.it = lo;
-            E.s = C->item[lo] & (SP_NS - 1);
-            const int t = C->item[lo] >> SP_SB;
-            const SpState Sx = sp_chunk_state(C, E.s);
-            const int cnt = Sx.w.get(t);
-            const bool aka = sp_aka_in_wall(Sx, t);
+            const int lo = (int)(w & 63u), d = (int)((w >> 6) & 63u), vidx = (int)((w >> 12) & 1u);
+            const int item = (int)C->item[lo], s = item & (SP_NS - 1), t = item >> SP_SB;
+            const SpState S = sp_chunk_state(C, s);
+#ifdef MJ_EMU
+            E.S = S;
+#endif
+            // The red-five rules in arithmetic: written as chains of comparisons (sp_aka_in_wall, akaize, the aka variant rule,
+            // sp_discard_prio) each of them compiles to nested exec regions.  A suit's plain five is tile 4 + 9 * suit, its red five
+            // T_5MR + suit = the plain one + 30 - 8 * suit; akas holds "red five in hand" at bit suit, "in the wall" at bit 3 + suit.
+            constexpr u64 FIVES = (1ull << T_5M) | (1ull << T_5P) | (1ull << T_5S);
+            const int st = (t * 57) >> 9, sd = (d * 57) >> 9;  // t / 9, d / 9 (exact below 64)
+            const int cnt = S.w.get(t);
+            const u32 aka = (u32)((FIVES >> t) & 1ull) & (S.akas >> (3 + st));  // sp_aka_in_wall(S, t)
             // the tile's draw entries: plain (all copies but the red one) if any, then the red five
-            const bool red = aka && (vidx == 1 || cnt < 2);
-            E.count = !aka ? cnt : red ? 1 : cnt - 1;
-            E.tile = red ? akaize(t) : t;
-            const u32 akas1 = red ? (Sx.akas | (1u << (E.tile - T_5MR))) : Sx.akas;  // akas_in_hand after the draw
-            const int c = Sx.h.get(d & 63);  // d != t: the draw does not change its count
-            int dt = d;  // aka variant rule (state.rs:116-121): the red five goes last
-            if (d == T_5M && (akas1 & 1) && c == 1) dt = T_5MR;
-            else if (d == T_5P && (akas1 & 2) && c == 1) dt = T_5PR;
-            else if (d == T_5S && (akas1 & 4) && c == 1) dt = T_5SR;
+            const u32 red = aka & (u32)(vidx | (cnt < 2 ? 1 : 0));
+            const int count = red ? 1 : cnt - (int)aka;
+            E.tile = t + (int)red * (30 - 8 * st);
+            const u32 akas1 = S.akas | (red << st);  // akas_in_hand after the draw
+            const int c = S.h.get(d);                // d != t: the draw does not change its count
+            // aka variant rule (state.rs:116-121): the red five goes last
+            const u32 redd = (u32)((FIVES >> d) & 1ull) & (akas1 >> sd) & (c == 1 ? 1u : 0u);
+            const int dt = d + (int)redd * (30 - 8 * sd);
             E.dt = dt;
-            E.dk = sp_dk_add(C->dk[E.s], E.tile, dt);
+            E.td = (u32)t | ((u32)d << 6) | (red << 12) | (redd << 13) | ((u32)s << 14);
+            E.dk = sp_dk_add<true>(C->dk[s], E.tile, dt);
             E.h = sp_dk_hash(E.dk);
+            const int pos = C->child_base[s] + (int)C->coff[lo] + (e - (int)C->eoff[lo]);
+            E.pos_out = E.on ? pos : SP_POOL;  // (an entry past the end stores nothing)
+            const int m = d - 9 * sd - 4, prio = redd ? 1 : d >= 27 ? 7 : 2 + (m < 0 ? -m : m);  // sp_discard_prio(dt)
+            E.ent = ((u32)(prio * 64 + (63 - dt)) << 15) | ((w >> 13) & 1u ? SP_ENT_LAST : 0u) | ((u32)count << 25);  // (bit 13: the last discard of the draw entry)
+#ifdef MJ_EMU  // the arithmetic against the rules as the rest of the file states them
+            if ((aka != 0) != sp_aka_in_wall(S, t) || E.tile != (red ? akaize(t) : t) || dt != (redd ? akaize(d) : d) ||
+                prio * 64 + (63 - dt) != sp_discard_key(dt))
+                X->overflow = 1;
+#endif
             return E;
         };
-        constexpr u32 HB = LDS_SET ? SP_SET_SLOTS : 0;  // the HBM table's first node slot
-        // `known`: what LDS answered, the slot (| 1 << 16: a way of the set claimed by this call = a fresh state), or -1: the HBM table,
-        // whose first look is `first_old`
-        auto finish = [&](const Ent& E, u64 first_old, int known) -> int {  // the rest of sp_insert after the first look, the list and the child entry
-            const u64 tag = SP_TAG(E.dk, tag_ep);
-            const SpState Sx = sp_chunk_state(C, E.s);
-            u32 pos = sp_hash_pos(E.h);
-            u64 old = first_old;
-            int cs = known >= 0 ? (known & 0xFFFF) : -1;
-            bool fresh = known >= 0 && (known >> 16) != 0;
+        // the child state, sp_apply(E.S, E.tile, E.dt) without a branch (Hand::inc / dec choose their word by one, deaka / is_aka by more)
+        auto child_of = [&](const Ent& E) -> SpState {
+            const u32 t = E.td & 63u, d = (E.td >> 6) & 63u, red = (E.td >> 12) & 1u, redd = (E.td >> 13) & 1u;
+            const u32 st = (t * 57u) >> 9, sd = (d * 57u) >> 9;
+            const u64 one_t = 1ull << (3 * (t < 18 ? t : t - 18)), one_d = 1ull << (3 * (d < 18 ? d : d - 18));
+            const SpState S = sp_chunk_state(C, (int)(E.td >> 14));  // (read again: a sixth of the entries get here, and held by value through
+            SpState R = S;                                            // the stages the two parents cost mj_k_sp five more spilled registers)
+            R.w.mp -= t < 18 ? one_t : 0ull;
+            R.w.sz -= t < 18 ? 0ull : one_t;
+            R.h.mp += (t < 18 ? one_t : 0ull) - (d < 18 ? one_d : 0ull);
+            R.h.sz += (t < 18 ? 0ull : one_t) - (d < 18 ? 0ull : one_d);
+            R.akas = ((S.akas & ~((red << 3) << st)) | (red << st)) & ~(redd << sd);
 #ifdef MJ_EMU
-            if (LDS_SET && known >= 0 && !fresh) sp_emu_check_hit(Wg, X, (u32)cs, E.dk, sp_apply(Sx, E.tile, E.dt));
-            if (!LDS_SET && known >= 0 && Wg->tag[known] != tag) X->overflow = 1;  // a cache hit must name the slot that holds this very state
+            const SpState Q = sp_apply(E.S, E.tile, E.dt);
+            if (Q.h.mp != R.h.mp || Q.h.sz != R.h.sz || Q.w.mp != R.w.mp || Q.w.sz != R.w.sz || Q.akas != R.akas) X->overflow = 1;
 #endif
-            if (fresh) sp_emu_placed(0);
-            for (int probe = 0; cs < 0 && probe < SP_CAP; probe++) {
-                if (old == 0ull) {
-                    fresh = true;
-                    cs = (int)(HB + pos);
-                    sp_emu_placed(1);
-                    break;
-                }
-                if (old == tag) {
-                    sp_emu_check_hit(Wg, X, HB + pos, E.dk, sp_apply(Sx, E.tile, E.dt));
-                    cs = (int)(HB + pos);
-                    break;
-                }
-                pos = (pos + 1) & (SP_CAP - 1);
-                old = Wg->tag[pos];
-                if (sp_tag_free(old, tag_ep)) old = sp_claim_tag(&Wg->tag[pos], tag, old);
-            }
-            if (cs < 0) X->overflow = 1;
-            if (fresh) sp_new_state(Wg, X, (u32)cs, E.dk, sp_apply(Sx, E.tile, E.dt));  // next list index: slot, key and id
-            const int pos_out = C->child_base[E.s] + (int)C->coff[E.it] + E.local;
-            const u32 ent = (cs < 0 ? SP_ENT_INVALID : (u32)cs) | ((u32)sp_discard_key(E.dt) << 15) | (E.rank == E.nk - 1 ? SP_ENT_LAST : 0u) |
-                            ((u32)E.count << 25);
-            if (pos_out < SP_POOL) Wg->pool[pos_out] = ent;
-            return cs;
+            return R;
         };
+        constexpr u32 HB = LDS_SET ? SP_SET_SLOTS : 0;  // the HBM table's first node slot
         // A child is looked up by ~6 parents, most of them neighbours in the level list, and five look-ups in six only need its slot.
-        // mj_k_sp: the states that found a way in the LDS set (sp_set_find_or_claim: most rows whole, the first part of the heaviest)
+        // mj_k_sp: the states that found a way in the LDS set (see sp_set_find_or_claim: most rows whole, the first part of the heaviest)
         // are found and placed there -- two ds_read_b128, one ds_cmpst per new state, no tag line from L2 / HBM (a 128-byte line per
         // 8-byte tag), no L2 atomic, no second round trip; only a state whose four ways belong to others goes on to the HBM table.
         // mj_k_sp_promo / mj_k_sp_wide (a parked row changes workgroups, LDS does not travel): a direct-mapped cache in LDS remembers
@@ -1214,43 +1222,175 @@ __device__ __forceinline__ void sp_expand_chunk(SpWork* W, SpCtx* X, SpChunk* C,
         u64* const set = X->set;
         SP_ASSUME_LDS(set);  // (a generic pointer would turn the look-up into a flat_load, which waits for every HBM gather in flight)
         const u64 cc_ep = (u64)X->cc_epoch << 42;
-        auto look = [&](const Ent& E) -> int {
-            if (!E.on) return -1;
+        // Stages 1-3 exist in two forms, for a round of one entry per lane and of two (uniform: a round with at most 64 entries does
+        // not pay for a second entry's selects, -0.9 % when the pass was per-lane code); 4-6 are one copy over two entries, the second
+        // of which is past the end in a round of one.
+        constexpr int NE = 2;
+        Ent E[NE];
+        // The gate of a stage: does ANY lane of the wavefront need it?  On the device a ballot and a scalar branch.  What sits behind a gate
+        // is predicated per lane, so the gate decides what is skipped, never what is computed; the emulator, whose lanes are fibers that
+        // run one after the other between collectives, takes the lane's own predicate for it -- the pass has no collective of its own, a
+        // lane inserts all its entries before the next lane runs, as it did when the pass was per-lane code, and the placements that
+        // tests/golden/sp_directed_hands.json records for that order stand.
+        auto any_lane = [](bool p) -> bool {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MJ_EMU)
+            return __ballot(p) != 0ull;
+#else
+            return p;
+#endif
+        };
+        // The child's slot: -1 while it is not known, | 1 << 16 if this lane created the child (a fresh state).  An entry past the end
+        // counts as known.  What a lane still has to do is kept in these integers, not in flags of their own: a flag that lives across
+        // a uniform branch is a lane mask in SGPRs, and every stage would begin by turning masks back into lanes.
+        int cs[NE];
+        auto front = [&](int e0, auto nf_c) {  // the entries e0 + i * SP_NT + tid, i < NF
+            constexpr int NF = decltype(nf_c)::value;
+            if (tid == 0) sp_emu_path(NF - 1);
+            // 1. decode, from einfo; the entries the layout pass did not leave there are searched for behind one test
+            {
+                u32 w[NF];
+#pragma unroll
+                for (int i = 0; i < NF; i++) {
+                    const int e = e0 + i * SP_NT + tid;
+                    w[i] = C->einfo[e < min(n_entries, SP_EINFO_CAP) ? e : 0];
+                }
+                if (min(e0 + NF * SP_NT, n_entries) > SP_EINFO_CAP) {
+#pragma unroll
+                    for (int i = 0; i < NF; i++) {
+                        const int e = e0 + i * SP_NT + tid;
+                        if (e >= SP_EINFO_CAP && e < n_entries) w[i] = einfo_search(e);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < NF; i++) E[i] = decode(e0 + i * SP_NT + tid, w[i]);
+            }
             if constexpr (LDS_SET) {
-                return sp_set_find_or_claim(set, E.h, SP_TAG(E.dk, tag_ep), tag_ep);
+                // 2. look: both buckets of every entry (one ds_read_b128 each, all issued together), then the way that holds the tag, or
+                // the first way free of this row's states in the fixed order bucket 1 way 0, way 1, bucket 2 way 0, way 1
+                struct alignas(16) Bucket { u64 w[2]; };
+                const Bucket* const bk = reinterpret_cast<const Bucket*>(set);
+                Bucket Bk[NF][2];
+                u32 way[NF];  // the next way to try; 4: nothing to claim (found, placed, all four ways belong to others, or past the end)
+#pragma unroll
+                for (int i = 0; i < NF; i++) Bk[i][0] = bk[sp_hash_b1(E[i].h)], Bk[i][1] = bk[sp_hash_b2(E[i].h)];
+#pragma unroll
+                for (int i = 0; i < NF; i++) {
+                    const u32 b1 = sp_hash_b1(E[i].h), b2 = sp_hash_b2(E[i].h);
+                    const u64 tag = SP_TAG(E[i].dk, tag_ep);
+                    const u64 w0 = Bk[i][0].w[0], w1 = Bk[i][0].w[1], w2 = Bk[i][1].w[0], w3 = Bk[i][1].w[1];
+                    const u32 hit = w0 == tag ? 0u : w1 == tag ? 1u : w2 == tag ? 2u : w3 == tag ? 3u : 4u;
+                    const u32 open = sp_tag_free(w0, tag_ep) ? 0u : sp_tag_free(w1, tag_ep) ? 1u : sp_tag_free(w2, tag_ep) ? 2u : sp_tag_free(w3, tag_ep) ? 3u : 4u;
+                    cs[i] = hit < 4u ? (int)(2 * (hit >> 1 ? b2 : b1) + (hit & 1u)) : E[i].on ? -1 : 0;
+                    way[i] = cs[i] < 0 ? open : 4u;
+                }
+                // 3. claim: a pending lane takes one way per turn of the loop -- it reads the way again, and if the way is still free of
+                // this row's states one ds_cmpst decides: won (a fresh state), the same id has just arrived there (another lane placed this
+                // very state), or on to the next way.  The walk is sp_set_find_or_claim's: same order, a way is never freed within a
+                // row, so every lane that looks for one id walks the same ways to the same end, whenever it looks.
+                for (int turn = 0; any_lane(min(way[0], way[NF - 1]) < 4u); turn++) {
+                    if (turn > 0) sp_emu_path(3);
+#pragma unroll
+                    for (int i = 0; i < NF; i++) {
+                        const u64 tag = SP_TAG(E[i].dk, tag_ep);
+                        const bool pend = way[i] < 4u;
+                        const u32 slot = 2 * (way[i] & 2u ? sp_hash_b2(E[i].h) : sp_hash_b1(E[i].h)) + (way[i] & 1u);  // (way 4: bucket 1 way 0, read for nothing)
+                        const u64 cur = set[slot];
+                        const bool open = pend && sp_tag_free(cur, tag_ep);
+                        u64 old = 1ull;
+                        if (open) {
+                            old = sp_claim_tag(&set[slot], tag, cur);
+                            if (old != 0ull) sp_emu_lost(2 + (old != tag ? 1 : 0));
+                            else sp_emu_placed(0);
+                        }
+                        const bool won = old == 0ull, here = pend && (won || cur == tag || old == tag);
+                        cs[i] = here ? (int)(slot | (won ? 1u << 16 : 0u)) : cs[i];
+                        way[i] = here ? 4u : way[i] + (pend ? 1u : 0u);
+                    }
+                }
+#ifdef MJ_EMU
+#pragma unroll
+                for (int i = 0; i < NF; i++)
+                    if (E[i].on && cs[i] >= 0 && (cs[i] >> 16) == 0) sp_emu_check_hit(Wg, X, (u32)cs[i], E[i].dk, sp_apply(E[i].S, E[i].tile, E[i].dt));
+#endif
             } else {
-                const u64 v = set[sp_hash_pos(E.h) & (SP_SET_SLOTS - 1)];
-                return (v >> 14) == (cc_ep | E.dk) ? (int)(v & 0x3FFFu) : -1;
+                // 2. look, in the child cache
+#pragma unroll
+                for (int i = 0; i < NF; i++) {
+                    const u64 v = set[sp_hash_pos(E[i].h) & (SP_SET_SLOTS - 1)];
+                    cs[i] = (v >> 14) == (cc_ep | E[i].dk) ? (int)(v & 0x3FFFu) : E[i].on ? -1 : 0;
+#ifdef MJ_EMU
+                    if (E[i].on && cs[i] >= 0 && Wg->tag[cs[i]] != SP_TAG(E[i].dk, tag_ep)) X->overflow = 1;  // a cache hit must name the slot that holds this very state
+#endif
+                }
+            }
+            if constexpr (NF < NE) {  // the second entry: past the end
+                E[1] = E[0];
+                E[1].pos_out = SP_POOL;
+                cs[1] = 0;
             }
         };
-        auto cc_put = [&](const Ent& E, int cs) {
-            if (!LDS_SET && cs >= 0) set[sp_hash_pos(E.h) & (SP_SET_SLOTS - 1)] = ((cc_ep | E.dk) << 14) | (u64)(u32)cs;
+        auto back = [&]() {
+            // 4. the HBM table, for the lanes the LDS table did not answer (mj_k_sp: its four ways belong to other states of the row, now
+            // and for good).  Five edges in six find their child already there: LOOK before claiming (a plain load; within a row a tag only
+            // ever goes from free -- zero or another row's epoch -- to its final value, so a stale value can only look free, which costs
+            // the atomic that would have been issued anyway; round 4: 144 M L2 atomics per launch became ~25 M).  All first looks are
+            // issued before the first claim, all claims before the first answer is read: an insert is one L2 round trip of latency and
+            // little else.
+            if (any_lane((cs[0] | cs[NE - 1]) < 0)) {
+                u64 old[NE];
+#pragma unroll
+                for (int i = 0; i < NE; i++) {
+                    old[i] = 1ull;
+                    if (cs[i] < 0) old[i] = Wg->tag[sp_hash_pos(E[i].h)];
+                }
+#pragma unroll
+                for (int i = 0; i < NE; i++)
+                    if (cs[i] < 0 && sp_tag_free(old[i], tag_ep)) old[i] = sp_claim_tag(&Wg->tag[sp_hash_pos(E[i].h)], SP_TAG(E[i].dk, tag_ep), old[i]);
+#pragma unroll
+                for (int i = 0; i < NE; i++) {
+                    if (cs[i] >= 0) continue;
+                    sp_emu_path(4);
+                    const u64 tag = SP_TAG(E[i].dk, tag_ep);
+                    u32 pos = sp_hash_pos(E[i].h);
+                    u64 o = old[i];
+#pragma unroll 1
+                    for (int probe = 0; probe < SP_CAP; probe++) {  // linear probe from the first look on
+                        if (o == 0ull) {
+                            cs[i] = (int)((HB + pos) | (1u << 16));
+                            sp_emu_placed(1);
+                            break;
+                        }
+                        if (o == tag) {
+#ifdef MJ_EMU
+                            sp_emu_check_hit(Wg, X, HB + pos, E[i].dk, sp_apply(E[i].S, E[i].tile, E[i].dt));
+#endif
+                            cs[i] = (int)(HB + pos);
+                            break;
+                        }
+                        sp_emu_path(5);
+                        pos = (pos + 1) & (SP_CAP - 1);
+                        o = Wg->tag[pos];
+                        if (sp_tag_free(o, tag_ep)) o = sp_claim_tag(&Wg->tag[pos], tag, o);
+                    }
+                    if (cs[i] < 0) X->overflow = 1;
+                    if (!LDS_SET && cs[i] >= 0) set[sp_hash_pos(E[i].h) & (SP_SET_SLOTS - 1)] = ((cc_ep | E[i].dk) << 14) | (u64)(u32)(cs[i] & 0xFFFF);
+                }
+            }
+            // 5. new states: the next list index, then the state is built (without a branch) and slot, key and id are written at that index.
+            // (One reservation per wavefront -- ballot prefix, one add -- is not worth a collective here: the compiler already folds the
+            // lanes' adds of an entry into one ds_add with a v_mbcnt prefix.)
+#pragma unroll
+            for (int i = 0; i < NE; i++)
+                if ((cs[i] >> 16) == 1) sp_new_state(Wg, X, (u32)(cs[i] & 0xFFFF), E[i].dk, child_of(E[i]));
+            // 6. the child-list entry, at the place the layout pass gave it
+#pragma unroll
+            for (int i = 0; i < NE; i++)
+                if (E[i].pos_out < SP_POOL) Wg->pool[E[i].pos_out] = (cs[i] < 0 ? SP_ENT_INVALID : (u32)(cs[i] & 0xFFFF)) | E[i].ent;
         };
         for (int e0 = 0; e0 < n_entries; e0 += 2 * SP_NT) {
-            const bool two = e0 + SP_NT < n_entries;  // uniform: a round with at most 64 entries decodes one entry per lane (-0.9 %)
-            const Ent A = decode(e0 + tid);
-            Ent B = A;
-            B.on = false;
-            if (two) B = decode(e0 + SP_NT + tid);
-            u64 oa = 1ull, ob = 1ull;
-            const int ka = look(A), kb = look(B);
-            // the HBM table.  Five edges in six find their child already there: LOOK before claiming (a plain load; within a row a tag
-            // only ever goes from free -- zero or another row's epoch -- to its final value, so a stale value can only look free, which
-            // costs the atomic that would have been issued anyway).  mj_k_sp -3.0 % (round 4, same box): 144 M L2 atomics per launch
-            // became ~25 M.
-            const u32 pa = sp_hash_pos(A.h), pb = sp_hash_pos(B.h);
-            if (A.on && ka < 0) oa = Wg->tag[pa];
-            if (B.on && kb < 0) ob = Wg->tag[pb];
-            if (A.on && ka < 0 && sp_tag_free(oa, tag_ep)) oa = sp_claim_tag(&Wg->tag[pa], SP_TAG(A.dk, tag_ep), oa);
-            if (B.on && kb < 0 && sp_tag_free(ob, tag_ep)) ob = sp_claim_tag(&Wg->tag[pb], SP_TAG(B.dk, tag_ep), ob);
-            if (A.on) {
-                const int cs = finish(A, oa, ka);
-                if (ka < 0) cc_put(A, cs);
-            }
-            if (B.on) {
-                const int cs = finish(B, ob, kb);
-                if (kb < 0) cc_put(B, cs);
-            }
+            if (e0 + SP_NT < n_entries) front(e0, std::integral_constant<int, 2>{});  // (uniform)
+            else front(e0, std::integral_constant<int, 1>{});
+            back();
         }
         mj_team_sync<SP_NT>();
         if (prof) {
